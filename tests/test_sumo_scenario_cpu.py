@@ -11,8 +11,25 @@ from dmdqn_amd.scenario import Grid
 from dmdqn_amd.sumo_scenario import (PHASE_DURATIONS, edge_index, load_scenario,
                                      scenario_tables)
 
-REF_CFG = "/root/reference/src/sumo_files/scenarios/grid_3x3.sumocfg"
+# the scenario's own SUMO files (config; net and duarouter routes gzipped), stored as data
+REF_DIR = os.path.join(GOLDEN, "grid_3x3")
 FIXTURE = os.path.join(GOLDEN, "grid_3x3_p06_scenario.npz")
+
+
+@pytest.fixture(scope="module")
+def ref_cfg(tmp_path_factory):
+    """The stored scenario unpacked into a temporary directory -> its .sumocfg."""
+    import gzip
+    import shutil
+    d = str(tmp_path_factory.mktemp("grid_3x3"))
+    for name in os.listdir(REF_DIR):
+        if name.endswith(".gz"):
+            with gzip.open(os.path.join(REF_DIR, name), "rb") as f, \
+                    open(os.path.join(d, name[:-3]), "wb") as g:
+                shutil.copyfileobj(f, g)
+        else:
+            shutil.copy(os.path.join(REF_DIR, name), d)
+    return os.path.join(d, "grid_3x3.sumocfg")
 
 
 def test_fixture_facts():
@@ -24,9 +41,8 @@ def test_fixture_facts():
     assert (sc.origin == sc.dest).sum() == 19                        # one-edge routes
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason="reference scenario not present")
-def test_loader_on_reference_files_matches_fixture():
-    a, b = load_scenario(REF_CFG), load_scenario(FIXTURE)
+def test_loader_on_reference_files_matches_fixture(ref_cfg):
+    a, b = load_scenario(ref_cfg), load_scenario(FIXTURE)
     np.testing.assert_array_equal(a.origin, b.origin)
     np.testing.assert_array_equal(a.dest, b.dest)
     np.testing.assert_array_equal(a.route, b.route)
@@ -132,7 +148,7 @@ def _traversed(env):
     return seq
 
 
-def test_vehicles_follow_their_scenario_routes():
+def test_vehicles_follow_their_scenario_routes(ref_cfg):
     """Every vehicle of the shipped scenario drives exactly its duarouter path
     (grid_3x3_p06.rou.xml:23-12524): over a full 240-step episode of the
     oracle simulator (which the HIP sim matches bit for bit, test_gpu_sim), each
@@ -159,12 +175,12 @@ def test_vehicles_follow_their_scenario_routes():
         assert got == want[:len(got)], (vid, got, want)
         full += got == want
     assert full >= arr  # every arrived vehicle drove its whole route
-    if os.path.exists(REF_CFG):  # and the words decode to the file's own edge lists
-        import xml.etree.ElementTree as ET
-        rou = os.path.join(os.path.dirname(REF_CFG), "grid_3x3_p06.rou.xml")
-        for i, v in enumerate(ET.parse(rou).getroot().iter("vehicle")):
-            edges = [edge_index(e, grid) for e in v.find("route").get("edges").split()]
-            assert route_edges(sc.route[i], sc.origin[i], grid) == edges
+    # and the words decode to the file's own edge lists
+    import xml.etree.ElementTree as ET
+    rou = os.path.join(os.path.dirname(ref_cfg), "grid_3x3_p06.rou.xml")
+    for i, v in enumerate(ET.parse(rou).getroot().iter("vehicle")):
+        edges = [edge_index(e, grid) for e in v.find("route").get("edges").split()]
+        assert route_edges(sc.route[i], sc.origin[i], grid) == edges
 
 
 def test_route_words_roundtrip_and_limits():

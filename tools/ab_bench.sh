@@ -11,7 +11,7 @@ for r in $(seq 1 "$rounds"); do
   i=0
   for v in "$@"; do
     echo "== $(date +%T) round $r variant $i: $v"
-    timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --no-stream-probe --steps ${AB_STEPS:-200} \
+    timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --no-stream-probe --steps ${AB_STEPS:-200} \
       $v > "$out/v${i}_r${r}.json" 2> "$out/v${i}_r${r}.err"
     rc=$?
     if [ $rc -ne 0 ]; then echo "rc=$rc"; tail -20 "$out/v${i}_r${r}.err"; exit $rc; fi

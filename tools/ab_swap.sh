@@ -19,7 +19,7 @@ for r in $(seq 1 "$rounds"); do
     name=$(basename "$lib" .so)
     cp "$lib" "$prod"
     echo "== $(date +%T) round $r $name"
-    timeout -k 10 300 python3 -u bench.py --no-cpu-baseline --no-stream-probe --steps ${AB_STEPS:-200} \
+    timeout -k 10 300 python3 -u bench.py --full --no-cpu-baseline --no-stream-probe --steps ${AB_STEPS:-200} \
       $bargs > "$out/${name}_r${r}.json" 2> "$out/${name}_r${r}.err"
     rc=$?
     if [ $rc -ne 0 ]; then echo "rc=$rc"; tail -20 "$out/${name}_r${r}.err"; exit $rc; fi

@@ -16,7 +16,7 @@ for v in "$@"; do
   if [ -n "$LEARN_ONLY" ]; then
     timeout -k 10 300 python3 tools/learn_bench.py 60 $BENCH_ARGS | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(\"$v\", d[\"median_ms\"], d[\"min_ms\"])"
   else
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline $BENCH_ARGS | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(\"$v\", d[\"value\"], d[\"roofline\"][\"avg_launch_ms\"], d[\"roofline\"][\"frac\"])"
+    timeout -k 10 300 python3 bench.py --full --no-cpu-baseline $BENCH_ARGS | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(\"$v\", d[\"value\"], d[\"roofline\"][\"avg_launch_ms\"], d[\"roofline\"][\"frac\"])"
   fi
 done
 cp /tmp/_cur_learn_h16.hpp $SRC

@@ -38,12 +38,12 @@ for step in "$@"; do
         --timeout-method thread -k "${step#tests=}" ;;
     bench_c2|bench_c3|bench_c5)
       c=${step#bench_}
-      run 400 "$out/$step.log" python -u bench.py --steps 200 --warmup 10 $(cfg $c) ${BENCH_ARGS:-}
+      run 400 "$out/$step.log" python -u bench.py --full --steps 200 --warmup 10 $(cfg $c) ${BENCH_ARGS:-}
       grep '^{' "$out/$step.log" > "$out/$step.json" ;;
     prof_c2|prof_c3|prof_c5)
       c=${step#prof_}
       run 500 "$out/$step.log" rocprofv3 --kernel-trace --stats -d "$out/$step" -o run -- \
-        python3 -u bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-stream-probe $(cfg $c) ;;
+        python3 -u bench.py --full --prefill-learn --steps 40 --warmup 5 --no-cpu-baseline --no-stream-probe $(cfg $c) ;;
     ab_revs)
       libs="dmdqn_amd/lib/libdmdqn_hip.so $(ls exp/libdmdqn_hip_*.so 2>/dev/null)"
       run 500 "$out/ab_revs.log" python -u tools/ab_learn_lib.py --rounds ${AB_ROUNDS:-6} $libs

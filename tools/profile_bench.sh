@@ -14,11 +14,11 @@ O=$R/gpurun_out
 mkdir -p $O/keep_$TAG
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$TAG -o run \
-    -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > $O/keep_$TAG/bench_prof.log 2>&1
+    -- python3 $R/bench.py --full --prefill-learn --steps 20 --warmup 5 --no-cpu-baseline "$@" > $O/keep_$TAG/bench_prof.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmcF_$TAG -o run \
-    -- python3 $R/bench.py --steps 4 --warmup 1 --prefill-steps 1100 --no-cpu-baseline "$@" > $O/pmcF_$TAG.log 2>&1
+    -- python3 $R/bench.py --full --prefill-learn --steps 4 --warmup 1 --prefill-steps 1100 --no-cpu-baseline "$@" > $O/pmcF_$TAG.log 2>&1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmcW_$TAG -o run \
-    -- python3 $R/bench.py --steps 4 --warmup 1 --prefill-steps 1100 --no-cpu-baseline "$@" > $O/pmcW_$TAG.log 2>&1
+    -- python3 $R/bench.py --full --prefill-learn --steps 4 --warmup 1 --prefill-steps 1100 --no-cpu-baseline "$@" > $O/pmcW_$TAG.log 2>&1
 F=$(find $O/pmcF_$TAG -name '*counter_collection.csv' | head -n 1)
 W=$(find $O/pmcW_$TAG -name '*counter_collection.csv' | head -n 1)
 cd $R
@@ -29,5 +29,5 @@ cp "$(find $O/prof_$TAG -name '*kernel_stats.csv' | head -n 1)" $O/keep_$TAG/ker
 gzip -c "$F" > $O/keep_$TAG/fetch_size_counter_collection.csv.gz
 gzip -c "$W" > $O/keep_$TAG/write_size_counter_collection.csv.gz
 # the un-profiled default bench line (HIP-event timing, with the CPU baseline)
-timeout -k 10 400 python3 bench.py "$@" > $O/keep_$TAG/bench.json 2> $O/keep_$TAG/bench.err
+timeout -k 10 400 python3 bench.py --full "$@" > $O/keep_$TAG/bench.json 2> $O/keep_$TAG/bench.err
 cat $O/keep_$TAG/bench.json

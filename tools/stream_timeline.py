@@ -5,7 +5,7 @@ the learn stream it prints, per step (learn start to the next learn start):
 the learn's duration, the gap before it, and what the other stream ran in
 that step (kernel, grid, start offset and duration, us).
 usage: python tools/stream_timeline.py run_kernel_trace.csv [learn-substring] [N] [skip]
-  skip: leave out the last `skip` learns (bench.py runs SIM_PROBE_STEPS = 10
+  skip: leave out the last `skip` learns (bench.py --full runs SIM_PROBE_STEPS = 10
   untimed steps after its timed region, with a V-bar reduction on the learn
   stream between them: pass 10 to see the timed steps only)"""
 import csv
