@@ -156,12 +156,14 @@ def call(name, *args):
 # include/dmdqn.h DMDQN_OPT_*: the launchers' test / A-B hooks, read from the
 # environment once at library load and changed only through set_option
 OPTIONS = {"sim_path": (0, {"auto": 0, "reg": 1, "lds": 2, "global": 3}),
-           "sample_tlog": (1, {None: 32})}
+           "sample_tlog": (1, {None: 32}),
+           "soft_path": (2, {"auto": 0, "fused": 1, "split": 2})}
 
 
 def set_option(name, value):
     """Set a run-time option (sim_path: auto | reg | lds | global; sample_tlog:
-    0..20 or None = no cap); returns the previous value in the same form."""
+    0..20 or None = no cap; soft_path: auto | fused | split); returns the
+    previous value in the same form."""
     which, names = OPTIONS[name]
     inv = {v: k for k, v in names.items()}
     lib = load()

@@ -9,6 +9,7 @@ stores or learns for every agent:
   remember(s, a, r, s', done)      DQNAgent.remember       (:312-326)
   replay()                         DQNAgent.replay / learn (:328-380, :428-434)
   update_target_network()          (:382-387)
+  update_target_network_soft()     (:389-399; cfg.tau > 0: fused into replay())
 
 Draw-order contract (bit-exact with the reference when E = 1 and the global
 streams are seeded with random.seed(s) / np.random.seed(s)): per env, agents
@@ -39,7 +40,7 @@ class CLearn(C.Structure):
         (n, C.c_float) for n in ["gamma", "alpha", "c1", "c2", "eps"]] + [
         ("stamps", C.c_void_p), ("qstats", C.c_void_p), ("params_h", C.c_void_p),
         ("loss_kind", C.c_int32), ("rn_out", C.c_void_p), ("row_format", C.c_int32),
-        ("xs", C.c_void_p), ("xn", C.c_void_p)]
+        ("xs", C.c_void_p), ("xn", C.c_void_p), ("tau", C.c_float), ("one_minus_tau", C.c_float)]
 
 
 # ctypes signatures of the learn entry points: the C-ABI tests call them
@@ -62,6 +63,8 @@ _lib.register({
                          C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p],
     "dmdqn_target_sync": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                           C.c_void_p],
+    "dmdqn_target_soft_update": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, C.c_float, C.c_float, C.c_void_p],
 })
 
 PRECISIONS = {"fp32": 0, "fp16": 1, "bf16": 2}
@@ -178,6 +181,27 @@ def keras_adam_consts(t, lr, b1=0.9, b2=0.999, eps=1e-7):
     return float(alpha), float(f(1 - b1)), float(f(1 - b2)), float(f(eps))
 
 
+def soft_update_consts(tau):
+    """(tau_f, omt_f) of the soft target update (update_target_network_soft,
+    dqn_agent.py:389-399) as the kernels receive them: float32(tau) and
+    float32(1.0 - tau), the subtraction in double as Python evaluates
+    `1.0 - self.tau`, rounded once."""
+    tau = float(tau)
+    return np.float32(tau), np.float32(1.0 - tau)
+
+
+def check_tau(tau, allow_zero=True):
+    """tau as a float, or ValueError: finite, in [0, 1] (0 = hard updates only)
+    or, for an explicit soft update, in (0, 1]."""
+    try:
+        t = float(tau)
+    except (TypeError, ValueError):
+        raise ValueError(f"tau must be a number, got {tau!r}") from None
+    if not (0.0 <= t <= 1.0) or (t == 0.0 and not allow_zero):
+        raise ValueError(f"tau must be in {'[' if allow_zero else '('}0, 1], got {tau!r}")
+    return t
+
+
 def keras_initial_weights(rng, hidden, n_agents):
     """HeNormal (truncated at 2 sigma, stddev sqrt(2/fan_in)/0.8796) for the ReLU
     layers, GlorotUniform for the output layer, zero biases (dqn_agent.py:160-181).
@@ -244,11 +268,26 @@ class AgentConfig:
     # s spare slots the trainer's "env" schedule lets its side stream run up to
     # s env steps ahead of the learn, which marks every s-th learn for it
     ring_spare: int = 16
+    # soft (Polyak) target updates, the reference's update_target_network_soft
+    # (dqn_agent.py:372-373, 389-399; docs/improvements.md item 9): after every
+    # learn target <- tau * online + (1 - tau) * target, fused into the learn
+    # kernels.  0 = off (the reference's training path).  The hard sync of
+    # target_update_frequency still runs when due and wins on that learn;
+    # target_update_frequency 0 = never hard-sync.
+    tau: float = 0.0
 
     @classmethod
     def from_dict(cls, d):
         known = {k: v for k, v in d.items() if k in cls.__dataclass_fields__}
         return cls(**known)
+
+
+def _soft_after_shared(agent, sync):
+    """The shared net's soft target update: one more launch on the one net
+    after its Adam step (every rank holds the same net and takes the same
+    step), unless this learn hard-synced (dqn_agent.py:372-377)."""
+    if agent.cfg.tau > 0 and not sync:
+        agent.update_target_network_soft()
 
 
 class BatchedDQN:
@@ -274,6 +313,9 @@ class BatchedDQN:
             raise ValueError(f"precision must be one of {list(PRECISIONS)}")
         if cfg.loss not in LOSSES:
             raise ValueError(f"loss must be one of {list(LOSSES)}")
+        check_tau(cfg.tau)
+        if int(cfg.target_update_frequency) < 0:
+            raise ValueError("target_update_frequency must be >= 0 (0 = never hard-sync)")
         if cfg.shared_params and (cfg.precision != "fp16" or H != 128):
             raise ValueError("shared_params needs precision 'fp16' and nn_layers [128, 128]")
         self.device = dev = torch.device(device)
@@ -485,7 +527,9 @@ class BatchedDQN:
             K.replay_sample(self.py_state, self.A, n, cfg.batch_size, out=self.idx)
         self.learn_step_counter += 1
         alpha, c1, c2, eps = keras_adam_consts(self.learn_step_counter, cfg.learning_rate)
-        sync = self.learn_step_counter % cfg.target_update_frequency == 0
+        # target_update_frequency 0: never hard-sync (soft updates alone)
+        sync = (cfg.target_update_frequency > 0
+                and self.learn_step_counter % cfg.target_update_frequency == 0)
         k = self.learn_step_counter % self.OUT_BUFS
         self.loss = self._loss_bufs[k]
         qstats = None
@@ -503,6 +547,7 @@ class BatchedDQN:
         brackets the range that starts at agent 0.  Returns self.loss."""
         alpha, c1, c2, eps, sync, qstats = self._last_learn
         cfg, ring = self.cfg, self.ring
+        tau_f, omt_f = soft_update_consts(cfg.tau)
         hook = self.learn_hook if lo == 0 else None
         if qstats is not None:
             qstats[lo:hi].zero_()  # the kernels accumulate into it
@@ -531,7 +576,8 @@ class BatchedDQN:
                                  sl(self.target), sl(self.target_h), sl(self.loss), ring.start,
                                  self.H, PRECISIONS[cfg.precision], sync, cfg.gamma, alpha, c1, c2,
                                  eps, LOSSES[cfg.loss], sl(qstats), sl(self.rn_out),
-                                 sl(self.stamps), grad=sl(self._split_grad), xs=xs, xn=xn)
+                                 sl(self.stamps), grad=sl(self._split_grad), xs=xs, xn=xn,
+                                 tau=float(tau_f), one_minus_tau=float(omt_f))
         if hook:
             hook(False)
         return self.loss
@@ -554,7 +600,8 @@ class BatchedDQN:
                       LOSSES[cfg.loss], None if self.rn_out is None else self.rn_out.data_ptr(),
                       int(self.ring.row_format == "f32"),
                       None if self._xs is None else self._xs.data_ptr(),
-                      None if self._xn is None else self._xn.data_ptr())
+                      None if self._xn is None else self._xn.data_ptr(),
+                      *soft_update_consts(cfg.tau))
 
     def presample(self, n, lds_budget=0):
         """Draw the next learn's replay indices now (ReplayBuffer.sample,
@@ -608,6 +655,7 @@ class BatchedDQN:
             self._ops.adam_slabs(self.params, self.adam_m, self.adam_v, self.target, self.target_h,
                                  self.params_h, self.slab, self.grad, 1.0 / self.NA, 1.0, alpha,
                                  c1, c2, eps, sync)
+            _soft_after_shared(self, sync)
             return
         if world > 1:
             # one flat 114 KB buffer per learn, bounded (dist.BoundedAllReduce:
@@ -625,6 +673,7 @@ class BatchedDQN:
             self.shared_paths["allreduce"] += 1
         self._ops.adam(self.params, self.adam_m, self.adam_v, self.target, self.target_h,
                        self.params_h, self.grad, 1.0 / world, alpha, c1, c2, eps, sync)
+        _soft_after_shared(self, sync)
 
     def drain_collectives(self):
         """Wait (bounded, dist.BoundedAllReduce.drain) for the shared net's
@@ -645,6 +694,15 @@ class BatchedDQN:
         """dqn_agent.py:382-387: target <- online, and the 16-bit shadow."""
         self._ops.target_sync(self.params, self.target, self.target_h,
                               PRECISIONS[self.cfg.precision])
+
+    def update_target_network_soft(self, tau=None):
+        """dqn_agent.py:389-399 outside a learn: target <- tau * online +
+        (1 - tau) * target for every net (three rounded f32 ops per parameter),
+        and the 16-bit shadow.  tau: cfg.tau by default; must be in (0, 1]."""
+        tau_f, omt_f = soft_update_consts(
+            check_tau(self.cfg.tau if tau is None else tau, allow_zero=False))
+        self._ops.target_soft_update(self.params, self.target, self.target_h,
+                                     PRECISIONS[self.cfg.precision], float(tau_f), float(omt_f))
 
     # -------------------------------------------------------------- weights
     def keras_params(self, which="params"):

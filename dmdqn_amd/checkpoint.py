@@ -42,12 +42,15 @@ _AGENT_TENSORS = ["params", "target", "adam_m", "adam_v", "np_state", "py_state"
 # derived state stale), so load() refuses it.
 _AGENT_FIXED = ["precision", "shared_params", "nn_layers", "replay_buffer_size", "batch_size",
                 "seed", "loss", "target_update_frequency", "count_env_steps", "replay_rows",
-                "ring_spare"]
+                "ring_spare", "tau"]
 _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features", "cap_lane",
               "end_ms", "period_ms", "step_duration", "max_sim_time", "action_stride", "scenario",
               "actuated"]
 # fields added after format 4 was introduced
-_DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2}
+# (tau: the soft target update's rate; a checkpoint saved before it existed
+# ran hard updates only)
+_DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2,
+             "tau": 0.0}
 
 
 def _written(total, ring):

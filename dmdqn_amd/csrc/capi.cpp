@@ -17,7 +17,7 @@ void set_error(const char *fmt, ...) {
 }
 
 // Run-time options (dmdqn.h DMDQN_OPT_*), from the environment at load time.
-static int g_opt[2] = {0, 32};
+static int g_opt[3] = {0, 32, 0};
 
 __attribute__((constructor)) static void read_options() {
     const char *p = getenv("DMDQN_SIM_PATH");
@@ -25,6 +25,8 @@ __attribute__((constructor)) static void read_options() {
                                        : !strcmp(p, "global") ? 3 : 0;
     const char *t = getenv("DMDQN_SAMPLE_TLOG");
     if (t && atoi(t) >= 0 && atoi(t) <= 20) g_opt[DMDQN_OPT_SAMPLE_TLOG] = atoi(t);
+    const char *s = getenv("DMDQN_SOFT_PATH");
+    if (s) g_opt[DMDQN_OPT_SOFT_PATH] = !strcmp(s, "fused") ? 1 : !strcmp(s, "split") ? 2 : 0;
 }
 
 int option(int which) { return g_opt[which]; }
@@ -59,8 +61,11 @@ extern "C" int dmdqn_debug_build(void) {
 }
 
 extern "C" int dmdqn_set_option(int opt, int value) {
-    DMDQN_REQUIRE(opt == DMDQN_OPT_SIM_PATH || opt == DMDQN_OPT_SAMPLE_TLOG,
+    DMDQN_REQUIRE(opt == DMDQN_OPT_SIM_PATH || opt == DMDQN_OPT_SAMPLE_TLOG ||
+                      opt == DMDQN_OPT_SOFT_PATH,
                   "dmdqn_set_option: unknown option %d", opt);
+    DMDQN_REQUIRE(opt != DMDQN_OPT_SOFT_PATH || (value >= 0 && value <= 2),
+                  "dmdqn_set_option: soft path %d (0 auto, 1 fused, 2 split)", value);
     DMDQN_REQUIRE(opt != DMDQN_OPT_SIM_PATH || (value >= 0 && value <= 3),
                   "dmdqn_set_option: sim path %d (0 auto, 1 reg, 2 lds, 3 global)", value);
     DMDQN_REQUIRE(opt != DMDQN_OPT_SAMPLE_TLOG || (value >= 0 && value <= 20) || value == 32,
@@ -70,7 +75,8 @@ extern "C" int dmdqn_set_option(int opt, int value) {
 }
 
 extern "C" int dmdqn_get_option(int opt) {
-    DMDQN_REQUIRE(opt == DMDQN_OPT_SIM_PATH || opt == DMDQN_OPT_SAMPLE_TLOG,
+    DMDQN_REQUIRE(opt == DMDQN_OPT_SIM_PATH || opt == DMDQN_OPT_SAMPLE_TLOG ||
+                      opt == DMDQN_OPT_SOFT_PATH,
                   "dmdqn_get_option: unknown option %d", opt);
     return dmdqn::g_opt[opt];
 }

@@ -302,6 +302,16 @@ __device__ __forceinline__ float mul_rn(float a, float b) {
     return p;
 }
 
+// The soft (Polyak) target update of one parameter
+// (DQNAgent.update_target_network_soft, dqn_agent.py:389-399): tau * online +
+// (1 - tau) * target as TF's three separate elementwise kernels round it -- two
+// rounded products, then the rounded sum (no fma).  Shared by the learn
+// epilogues and k_target_soft, so a fused soft learn and a plain learn followed
+// by dmdqn_target_soft_update leave the same bits.
+__device__ __forceinline__ float soft_el(float w, float t, float tau, float omt) {
+    return mul_rn(tau, w) + mul_rn(omt, t);
+}
+
 __device__ __forceinline__ void loss_term(int kind, float diff, float inv_b, float &term,
                                           float &dq) {
     if (kind == DMDQN_LOSS_HUBER) {

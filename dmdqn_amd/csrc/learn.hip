@@ -5,7 +5,8 @@
 //   gather S, S' rows (int8 replay rows -> LDS), z-score the f64 rewards with
 //   numpy's pairwise order, a* = argmax online(S'), q_t = target(S')[a*],
 //   y = r + gamma (1-d) q_t, q = online(S)[a], L = mean((y-q)^2), backward
-//   through the 3 Dense layers, Keras-3 Adam, optional target <- online.
+//   through the 3 Dense layers, Keras-3 Adam, optional target <- online, or
+//   the soft update target <- tau * online + (1 - tau) * target (:389-399).
 // All three GEMM chains run on MFMA (v_mfma_f32_16x16x4_f32: exact f32
 // products, the strict-parity path).  Work split per layer: 8 waves x one
 // 16-wide output-column tile each; the batch (128 rows) is the M dimension.
@@ -124,6 +125,8 @@ __device__ void forward(const float *P, const TX *X, float *H1, float *H2, float
 
 struct AdamK {
     float alpha, c1, c2, eps;
+    float tau, omt;  // soft target update (dqn_agent.py:389-399) when soft
+    bool soft;
 };
 
 // Keras-3 Adam (keras/src/optimizers/adam.py update_step) for one element.
@@ -138,7 +141,8 @@ __device__ __forceinline__ void adam_el(float *w, float *m, float *v, float *tgt
     m[i] = mi;
     v[i] = vi;
     w[i] = wi;
-    if (sync) tgt[i] = wi;
+    if (sync) tgt[i] = wi;  // the hard copy wins over the soft rule (:372-377)
+    else if (K.soft) tgt[i] = soft_el(wi, tgt[i], K.tau, K.omt);
 }
 
 // XF: float replay rows (DMDQN_ROWS_F32): X(S') / X(S) are read as f32 from the
@@ -161,7 +165,7 @@ __global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a) {
     float *Wp = a.params + agent * P, *Mp = a.adam_m + agent * P, *Vp = a.adam_v + agent * P;
     float *Tp = a.target + agent * P;
     const bool sync = a.sync_target != 0;
-    const AdamK AK{a.alpha, a.c1, a.c2, a.eps};
+    const AdamK AK{a.alpha, a.c1, a.c2, a.eps, a.tau, a.one_minus_tau, a.tau > 0.0f};
 
     // ---- P0: batch metadata (ReplayBuffer.sample :63-64 via deque positions)
     if (tid < B_) {
@@ -477,6 +481,51 @@ int launch_learn_grad_f16(const dmdqn_learn_args *a, float *grad, hipStream_t s)
 int launch_learn_grad_bf16(const dmdqn_learn_args *a, float *grad, hipStream_t s);
 int launch_adam_agents_f16(const dmdqn_learn_args *a, const float *grad, hipStream_t s);
 int launch_adam_agents_bf16(const dmdqn_learn_args *a, const float *grad, hipStream_t s);
+int check_tau(const char *who, float tau, float omt, bool zero_ok);
+
+// Soft target update outside a learn (dqn_agent.py:389-399,
+// update_target_network_soft): target <- soft_el(params, target) for NW nets of
+// P parameters, and the 16-bit shadow (RNE cast of the new f32 target) when
+// target_h is given.  One lane per 4 consecutive parameters (16-byte f32
+// accesses, one 8-byte shadow store); P4 = P / 4 lanes per net, n4 = NW * P4.
+template <typename T16>
+__global__ void __launch_bounds__(256) k_target_soft(const float *params, float *target,
+                                                     T16 *target_h, int P4, int Ph, long n4,
+                                                     float tau, float omt) {
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n4) return;
+    const float4 w = reinterpret_cast<const float4 *>(params)[q];
+    float4 t = reinterpret_cast<const float4 *>(target)[q];
+    t.x = soft_el(w.x, t.x, tau, omt);
+    t.y = soft_el(w.y, t.y, tau, omt);
+    t.z = soft_el(w.z, t.z, tau, omt);
+    t.w = soft_el(w.w, t.w, tau, omt);
+    reinterpret_cast<float4 *>(target)[q] = t;
+    if (target_h) {
+        const long net = q / P4, k = q - net * P4;
+        typedef T16 t16x4 __attribute__((ext_vector_type(4)));
+        t16x4 hv;
+        hv[0] = (T16)t.x; hv[1] = (T16)t.y; hv[2] = (T16)t.z; hv[3] = (T16)t.w;
+        *reinterpret_cast<t16x4 *>(target_h + net * Ph + 4 * k) = hv;
+    }
+}
+
+// The launch behind dmdqn_target_soft_update; also the second launch of a
+// 16-bit soft learn that does not run fused (learn_h16.hpp: target_h == NULL,
+// or fewer agents than SOFT_FUSED_MIN_NA).
+int launch_target_soft(const float *params, float *target, uint16_t *target_h, int NW, int P,
+                       int Ph, int precision, float tau, float omt, hipStream_t s) {
+    const long n4 = (long)NW * (P / 4);
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    if (precision == 2)
+        hipLaunchKernelGGL(k_target_soft<__bf16>, grid, dim3(256), 0, s, params, target,
+                           reinterpret_cast<__bf16 *>(target_h), P / 4, Ph, n4, tau, omt);
+    else
+        hipLaunchKernelGGL(k_target_soft<_Float16>, grid, dim3(256), 0, s, params, target,
+                           reinterpret_cast<_Float16 *>(target_h), P / 4, Ph, n4, tau, omt);
+    DMDQN_LAUNCH_CHECK("k_target_soft");
+    return DMDQN_OK;
+}
 
 DMDQN_DBG_READER(dbg_flags_learn)
 
@@ -502,7 +551,20 @@ static int check_learn_args(const dmdqn_learn_args *a) {
     return DMDQN_OK;
 }
 
+// The soft target update's constants (dmdqn_learn_args.tau / .one_minus_tau):
+// tau finite in [0, 1] (zero_ok: 0 = off) or (0, 1], and one_minus_tau in
+// [0, 1] when the update is on.  The negated comparisons refuse a NaN.
+int dmdqn::check_tau(const char *who, float tau, float omt, bool zero_ok) {
+    DMDQN_REQUIRE(tau >= 0.0f && tau <= 1.0f && (zero_ok || tau > 0.0f),
+                  "%s: tau=%g must be in %s0, 1]", who, (double)tau, zero_ok ? "[" : "(");
+    DMDQN_REQUIRE(!(tau > 0.0f) || (omt >= 0.0f && omt <= 1.0f),
+                  "%s: one_minus_tau=%g must be in [0, 1]", who, (double)omt);
+    return DMDQN_OK;
+}
+
 extern "C" int dmdqn_learn(const dmdqn_learn_args *a, void *stream) {
+    DMDQN_REQUIRE(a, "dmdqn_learn: null args");
+    if (int rc = check_tau("dmdqn_learn", a->tau, a->one_minus_tau, true)) return rc;
     if (int rc = check_learn_args(a)) return rc;
     if (a->precision == 1) return launch_learn_f16(a, as_stream(stream));
     if (a->precision == 2) return launch_learn_bf16(a, as_stream(stream));
@@ -537,6 +599,7 @@ extern "C" int dmdqn_adam_agents(const dmdqn_learn_args *a, const float *grad, v
                   "dmdqn_adam_agents: null argument");
     DMDQN_REQUIRE(a->precision == 1 || a->precision == 2,
                   "dmdqn_adam_agents: precision %d (fp16 / bf16 only)", a->precision);
+    if (int rc = check_tau("dmdqn_adam_agents", a->tau, a->one_minus_tau, true)) return rc;
     return a->precision == 1 ? launch_adam_agents_f16(a, grad, as_stream(stream))
                              : launch_adam_agents_bf16(a, grad, as_stream(stream));
 }
@@ -605,4 +668,22 @@ extern "C" int dmdqn_target_sync(const float *params, float *target, uint16_t *t
                            target, reinterpret_cast<_Float16 *>(target_h), P, Ph, n);
     DMDQN_LAUNCH_CHECK("k_target_sync");
     return DMDQN_OK;
+}
+
+extern "C" int dmdqn_target_soft_update(const float *params, float *target, uint16_t *target_h,
+                                        int NW, int P, int Ph, int precision, float tau,
+                                        float one_minus_tau, void *stream) {
+    DMDQN_REQUIRE(params && target && NW > 0 && P > 0 && Ph >= P,
+                  "dmdqn_target_soft_update: NW=%d P=%d Ph=%d", NW, P, Ph);
+    DMDQN_REQUIRE(precision >= 0 && precision <= 2, "dmdqn_target_soft_update: precision %d",
+                  precision);
+    DMDQN_REQUIRE(!target_h || precision != 0,
+                  "dmdqn_target_soft_update: fp32 has no 16-bit shadow");
+    DMDQN_REQUIRE(P % 4 == 0 && (!target_h || Ph % 4 == 0),
+                  "dmdqn_target_soft_update: P=%d and Ph=%d must be multiples of 4", P, Ph);
+    DMDQN_REQUIRE(((uintptr_t)params | (uintptr_t)target) % 16 == 0 && (uintptr_t)target_h % 8 == 0,
+                  "dmdqn_target_soft_update: params / target must be 16-byte aligned, target_h 8");
+    if (int rc = check_tau("dmdqn_target_soft_update", tau, one_minus_tau, false)) return rc;
+    return launch_target_soft(params, target, target_h, NW, P, Ph, precision, tau, one_minus_tau,
+                              as_stream(stream));
 }

@@ -444,13 +444,37 @@ __device__ __forceinline__ void adam_el(float &w, float &m, float &v, float g, f
     w = w - (m * alpha) / (sqrtf(v) + eps);
 }
 
+// What a learn's Adam epilogue does to the target network (compile-time in the
+// kernels: no run-time branch in the Adam streams): nothing, the hard copy
+// target <- online (dqn_agent.py:376-387), or the soft update target <-
+// tau * online + (1 - tau) * target (update_target_network_soft, :389-399).
+constexpr int TGT_NONE = 0, TGT_HARD = 1, TGT_SOFT = 2;
+
 struct AdamC {
     float alpha, c1, c2, eps;
-    bool sync;
-    h16 *TH;    // f16 target copy written on syncs (or null)
+    int tmode;  // TGT_*
+    h16 *TH;    // f16 target copy written on syncs and soft updates (or null)
     bool gout;  // compile-time: write the 16-bit gradient to G instead of the
     float *G;   // Adam step (split learn: dmdqn_learn_grad + dmdqn_adam_agents)
+    float tau, omt;  // TGT_SOFT: float32(tau), float32(1 - tau)
 };
+
+// The soft update of a lane's 4 parameters: t (the f32 target loaded with w, m,
+// v) becomes soft_el(w, t), stored to T and, rounded to 16 bits, to TH.
+__device__ __forceinline__ void soft4(float *T, h16 *TH, size_t i, const float4 &w, float4 t,
+                                      const AdamC &k) {
+    t.x = soft_el(w.x, t.x, k.tau, k.omt);
+    t.y = soft_el(w.y, t.y, k.tau, k.omt);
+    t.z = soft_el(w.z, t.z, k.tau, k.omt);
+    t.w = soft_el(w.w, t.w, k.tau, k.omt);
+    *reinterpret_cast<float4 *>(T + i) = t;
+    if (TH) {
+        half4v hv;
+        hv[0] = (h16)t.x; hv[1] = (h16)t.y;
+        hv[2] = (h16)t.z; hv[3] = (h16)t.w;
+        *reinterpret_cast<half4v *>(TH + i) = hv;
+    }
+}
 
 // Keras-3 Adam on NT groups of 4 consecutive parameters (one 16-byte lane
 // access each).  All w, m, v loads of the NT groups are issued before any
@@ -465,12 +489,14 @@ __device__ __forceinline__ void adam4n(float *W, float *M, float *V, float *T, c
                 make_float4(gval(g[q], 0), gval(g[q], 1), gval(g[q], 2), gval(g[q], 3));
         return;
     }
-    float4 w[NT], m[NT], v[NT];
+    float4 w[NT], m[NT], v[NT], tg[NT];
 #pragma unroll
     for (int q = 0; q < NT; q++) {
         w[q] = *reinterpret_cast<const float4 *>(W + idx[q]);
         m[q] = *reinterpret_cast<const float4 *>(M + idx[q]);
         v[q] = *reinterpret_cast<const float4 *>(V + idx[q]);
+        // soft update: the old target rides the same round trip
+        if (k.tmode == TGT_SOFT) tg[q] = *reinterpret_cast<const float4 *>(T + idx[q]);
     }
     // keep all 3*NT loads in flight together: under VGPR pressure the
     // scheduler would otherwise sink each load to its use (one round trip each)
@@ -487,7 +513,7 @@ __device__ __forceinline__ void adam4n(float *W, float *M, float *V, float *T, c
         *reinterpret_cast<float4 *>(W + idx[q]) = w[q];
         *reinterpret_cast<float4 *>(M + idx[q]) = m[q];
         *reinterpret_cast<float4 *>(V + idx[q]) = v[q];
-        if (k.sync) {
+        if (k.tmode == TGT_HARD) {
             *reinterpret_cast<float4 *>(T + idx[q]) = w[q];
             if (k.TH) {
                 half4v hv;
@@ -496,6 +522,7 @@ __device__ __forceinline__ void adam4n(float *W, float *M, float *V, float *T, c
                 *reinterpret_cast<half4v *>(k.TH + idx[q]) = hv;
             }
         }
+        if (k.tmode == TGT_SOFT) soft4(T, k.TH, idx[q], w[q], tg[q], k);
     }
 }
 
@@ -524,6 +551,14 @@ __device__ __forceinline__ void adam4n(float *W, float *M, float *V, float *T, c
 #ifndef DMDQN_EARLY_W1
 #define DMDQN_EARLY_W1 1
 #endif
+// Soft target update in the pipe: 1 = the old target of batch h is loaded at
+// the top of iteration h, ahead of batch h+1's w, m, v (vmcnt is in-order, so
+// its wait does not cover them): one buffer, 4 NT fewer live VGPRs; 0 = it is
+// double-buffered with w, m, v.  Measured (C3 and C2, fp16 and bf16): 1 is
+// 2.7-4 % faster, scratch 84 -> 44-52 B per lane.
+#ifndef DMDQN_SOFT_TG_SINGLE
+#define DMDQN_SOFT_TG_SINGLE 1
+#endif
 // `valid(tile)` says whether the lane's 4 parameters of that tile exist (the
 // W1 block stores only features 0..88; a lane with nothing to update keeps its
 // registers and touches no memory).
@@ -545,7 +580,7 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
                     make_float4(gval(g[t], 0), gval(g[t], 1), gval(g[t], 2), gval(g[t], 3));
         return;
     }
-    float4 w[2][NT], m[2][NT], v[2][NT];
+    float4 w[2][NT], m[2][NT], v[2][NT], tg[2][NT];
     if constexpr (!EARLY) grad();
 #pragma unroll
     for (int q = 0; q < NT; q++) {
@@ -555,6 +590,8 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
             w[0][q] = *reinterpret_cast<const float4 *>(W + i);
             m[0][q] = *reinterpret_cast<const float4 *>(M + i);
             v[0][q] = *reinterpret_cast<const float4 *>(V + i);
+            if (!DMDQN_SOFT_TG_SINGLE && k.tmode == TGT_SOFT)
+                tg[0][q] = *reinterpret_cast<const float4 *>(T + i);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -564,7 +601,13 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
     }
 #pragma unroll
     for (int h = 0; h < NB; h++) {
-        const int c = h & 1, n = c ^ 1;
+        const int c = h & 1, n = c ^ 1, ct = DMDQN_SOFT_TG_SINGLE ? 0 : c;
+        if (DMDQN_SOFT_TG_SINGLE && k.tmode == TGT_SOFT) {
+#pragma unroll
+            for (int q = 0; q < NT; q++)
+                if (valid(h * NT + q))
+                    tg[0][q] = *reinterpret_cast<const float4 *>(T + ix(h * NT + q));
+        }
         if (h + 1 < NB) {
 #pragma unroll
             for (int q = 0; q < NT; q++) {
@@ -574,6 +617,8 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
                     w[n][q] = *reinterpret_cast<const float4 *>(W + i);
                     m[n][q] = *reinterpret_cast<const float4 *>(M + i);
                     v[n][q] = *reinterpret_cast<const float4 *>(V + i);
+                    if (!DMDQN_SOFT_TG_SINGLE && k.tmode == TGT_SOFT)
+                        tg[n][q] = *reinterpret_cast<const float4 *>(T + i);
                 }
             }
         }
@@ -593,7 +638,7 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
             *reinterpret_cast<float4 *>(W + i) = w[c][q];
             *reinterpret_cast<float4 *>(M + i) = m[c][q];
             *reinterpret_cast<float4 *>(V + i) = v[c][q];
-            if (k.sync) {
+            if (k.tmode == TGT_HARD) {
                 *reinterpret_cast<float4 *>(T + i) = w[c][q];
                 if (k.TH) {
                     half4v hv;
@@ -602,6 +647,7 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
                     *reinterpret_cast<half4v *>(k.TH + i) = hv;
                 }
             }
+            if (k.tmode == TGT_SOFT) soft4(T, k.TH, i, w[c][q], tg[ct][q], k);
         }
     }
 }
@@ -617,14 +663,20 @@ __device__ __forceinline__ void adam1(float *W, float *M, float *V, float *T, si
         k.G[i] = r16(g);
         return;
     }
-    float m = M[i], v = V[i], w = W[i];
+    float m = M[i], v = V[i], w = W[i], tg = 0.0f;
+    if (k.tmode == TGT_SOFT) tg = T[i];
     adam_el(w, m, v, r16(g), k.alpha, k.c1, k.c2, k.eps);  // the 16-bit gradient
     M[i] = m;
     V[i] = v;
     W[i] = w;
-    if (k.sync) {
+    if (k.tmode == TGT_HARD) {
         T[i] = w;
         if (k.TH) k.TH[i] = (h16)w;
+    }
+    if (k.tmode == TGT_SOFT) {
+        tg = soft_el(w, tg, k.tau, k.omt);
+        T[i] = tg;
+        if (k.TH) k.TH[i] = (h16)tg;
     }
 }
 
@@ -991,10 +1043,13 @@ __device__ __forceinline__ void bwd_dz1(h16 *R1, const uint32_t *mask, const f32
 
 // ----------------------------------------------------------------------------
 // Independent agents: one workgroup per agent, Adam fused on the gradient tiles.
-// QSTATS: also emit the learn metrics (a.qstats != NULL).  SYNC: this learn
-// ends with the hard target copy (a.sync_target): a compile-time constant, so
-// the Adam streams of the other 499 of 500 learns carry no branch (a branch
-// there makes the vmcnt waits conservative).  GOUT: the split learn -- every
+// QSTATS: also emit the learn metrics (a.qstats != NULL).  TM: what this learn
+// does to the target (TGT_NONE; TGT_HARD, the hard copy of a.sync_target;
+// TGT_SOFT, the soft update of a.tau): a compile-time constant, so the Adam
+// streams of the other 499 of 500 learns carry no branch (a branch there makes
+// the vmcnt waits conservative).  TGT_SOFT is instantiated for TS and !GOUT
+// only; without a shadow, or for few agents, the launcher runs TGT_NONE and
+// then k_target_soft (H16_LAUNCH).  GOUT: the split learn -- every
 // gradient entry goes to gout[agent][P] (the 16-bit value Adam would receive)
 // and dmdqn_adam_agents applies the identical Adam step in a second launch,
 // which can share the chip with the next step's side-stream work.
@@ -1002,7 +1057,7 @@ __device__ __forceinline__ void bwd_dz1(h16 *R1, const uint32_t *mask, const f32
 // a compile-time choice, because a run-time branch between the two fragment
 // sources made the loaded registers meet at a control-flow merge, where the
 // compiler waits for every load (round 5).
-template <bool QSTATS, bool SYNC, bool GOUT, bool XF = false, bool TS = true>
+template <bool QSTATS, int TM, bool GOUT, bool XF = false, bool TS = true>
 __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, float *gout) {
     LEARN_SMEM_SETUP;
     const int agent = blockIdx.x;
@@ -1012,8 +1067,9 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
     float *Tp = a.target + agent * Pz;
     const size_t Ph = (Pz + 7) / 8 * 8;
     h16 *TH = TS ? reinterpret_cast<h16 *>(a.target_h) + agent * Ph : nullptr;
-    const AdamC AK{a.alpha, a.c1, a.c2, a.eps, SYNC && !GOUT, TH, GOUT,
-                   GOUT ? gout + agent * Pz : nullptr};
+    static_assert(TM != TGT_SOFT || (TS && !GOUT), "soft: with the shadow, fused learn only");
+    const AdamC AK{a.alpha, a.c1, a.c2, a.eps, GOUT ? TGT_NONE : TM, TH, GOUT,
+                   GOUT ? gout + agent * Pz : nullptr, a.tau, a.one_minus_tau};
     STAMP(0);
     // Issue order (vmcnt is in-order): the deque positions, the output layers,
     // then the target's fragments -- so the slot computation waits only for
@@ -1063,7 +1119,7 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
     STAMP(7);
     const half8 ones = ones8();
 #if DMDQN_EARLY_W3
-    static_assert(!GOUT, "the early-W3 variant has no split form");
+    static_assert(!GOUT && TM != TGT_SOFT, "the early-W3 variant has no split or soft form");
     // ---- dW3[k][a] = H2^T . DQ (wave w: k-tile w) ; db3 (wave 0).  W3's
     // Adam loads (lanes lr < 4: rows k = 16w + 4lg + e, column a -> W3T[a][k..k+3])
     // are issued before the loss, so their latency hides behind it.
@@ -1092,7 +1148,7 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
             *reinterpret_cast<float4 *>(Wp + i3) = w3;
             *reinterpret_cast<float4 *>(Mp + i3) = m3;
             *reinterpret_cast<float4 *>(Vp + i3) = v3;
-            if (SYNC) {
+            if (TM == TGT_HARD) {
                 *reinterpret_cast<float4 *>(Tp + i3) = w3;
                 if (TH) {
                     half4v hv;
@@ -1211,13 +1267,15 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
 }
 
 // The split learn's second launch: Keras-3 Adam (adam_el, the fused kernel's
-// arithmetic) on every agent's P parameters from grad[NA][P]; on a sync also
-// the f32 target and its 16-bit shadow (agent stride Ph).  One lane per 4
-// consecutive parameters, blockIdx.y = agent.
-template <bool SYNC>
+// arithmetic) on every agent's P parameters from grad[NA][P]; on a sync (TM =
+// TGT_HARD) or a soft update (TGT_SOFT, soft_el with the old target loaded
+// beside w, m, v) also the f32 target and its 16-bit shadow (agent stride Ph).
+// One lane per 4 consecutive parameters, blockIdx.y = agent.
+template <int TM>
 __global__ void __launch_bounds__(256) H16_ADAM_KERNEL(float *W, float *M, float *V, float *T,
                                                        h16 *TH, const float *G, float alpha,
-                                                       float c1, float c2, float eps) {
+                                                       float c1, float c2, float eps, float tau,
+                                                       float omt) {
     constexpr int P4 = L::P / 4;
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= P4) return;
@@ -1226,6 +1284,8 @@ __global__ void __launch_bounds__(256) H16_ADAM_KERNEL(float *W, float *M, float
     float4 w = *reinterpret_cast<const float4 *>(W + i), m = *reinterpret_cast<const float4 *>(M + i);
     float4 v = *reinterpret_cast<const float4 *>(V + i);
     const float4 g = *reinterpret_cast<const float4 *>(G + i);
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (TM == TGT_SOFT) t = *reinterpret_cast<const float4 *>(T + i);
     float *pw = &w.x, *pm = &m.x, *pv = &v.x;
     const float *pg = &g.x;
 #pragma unroll
@@ -1233,7 +1293,7 @@ __global__ void __launch_bounds__(256) H16_ADAM_KERNEL(float *W, float *M, float
     *reinterpret_cast<float4 *>(W + i) = w;
     *reinterpret_cast<float4 *>(M + i) = m;
     *reinterpret_cast<float4 *>(V + i) = v;
-    if (SYNC) {
+    if (TM == TGT_HARD) {
         *reinterpret_cast<float4 *>(T + i) = w;
         if (TH) {
             half4v hv;
@@ -1242,18 +1302,45 @@ __global__ void __launch_bounds__(256) H16_ADAM_KERNEL(float *W, float *M, float
             *reinterpret_cast<half4v *>(TH + (size_t)blockIdx.y * Ph + 4 * (size_t)q) = hv;
         }
     }
+    if (TM == TGT_SOFT) {
+        t.x = soft_el(w.x, t.x, tau, omt);
+        t.y = soft_el(w.y, t.y, tau, omt);
+        t.z = soft_el(w.z, t.z, tau, omt);
+        t.w = soft_el(w.w, t.w, tau, omt);
+        *reinterpret_cast<float4 *>(T + i) = t;
+        if (TH) {
+            half4v hv;
+            hv[0] = (h16)t.x; hv[1] = (h16)t.y;
+            hv[2] = (h16)t.z; hv[3] = (h16)t.w;
+            *reinterpret_cast<half4v *>(TH + (size_t)blockIdx.y * Ph + 4 * (size_t)q) = hv;
+        }
+    }
 }
 
 DMDQN_DBG_READER(dbg_flags)
 
 // The kernel instance for a run-time target-shadow flag (TS above).
-template <bool QSTATS, bool SYNC, bool GOUT, bool XF>
+template <bool QSTATS, int TM, bool GOUT, bool XF>
 void (*pick_learn(bool ts))(dmdqn_learn_args, float *) {
-    return ts ? H16_LEARN_KERNEL<QSTATS, SYNC, GOUT, XF, true>
-              : H16_LEARN_KERNEL<QSTATS, SYNC, GOUT, XF, false>;
+    return ts ? H16_LEARN_KERNEL<QSTATS, TM, GOUT, XF, true>
+              : H16_LEARN_KERNEL<QSTATS, TM, GOUT, XF, false>;
+}
+
+// The fused learn's instance for a run-time target mode; TGT_SOFT exists with
+// the shadow only (the caller passes TGT_NONE otherwise).
+template <bool QSTATS, bool XF>
+void (*pick_learn_tm(int tm, bool ts))(dmdqn_learn_args, float *) {
+    if (tm == TGT_SOFT) return H16_LEARN_KERNEL<QSTATS, TGT_SOFT, false, XF, true>;
+    return tm == TGT_HARD ? pick_learn<QSTATS, TGT_HARD, false, XF>(ts)
+                          : pick_learn<QSTATS, TGT_NONE, false, XF>(ts);
 }
 
 }  // namespace H16K
+
+int launch_target_soft(const float *params, float *target, uint16_t *target_h, int NW, int P,
+                       int Ph, int precision, float tau, float omt, hipStream_t s);  // learn.hip
+// DMDQN_OPT_SOFT_PATH auto: fuse the soft target update from this many agents up
+constexpr int SOFT_FUSED_MIN_NA = 2048;
 
 int H16_LAUNCH(const dmdqn_learn_args *a, hipStream_t s) {
     DMDQN_REQUIRE(a->hidden == 128 && a->P == H16K::L::P,
@@ -1261,17 +1348,25 @@ int H16_LAUNCH(const dmdqn_learn_args *a, hipStream_t s) {
                   H16K::L::P);
     using namespace H16K;
     const bool ts = a->target_h != nullptr;
-    auto kern = a->qstats ? (a->sync_target ? pick_learn<true, true, false, false>(ts)
-                                            : pick_learn<true, false, false, false>(ts))
-                          : (a->sync_target ? pick_learn<false, true, false, false>(ts)
-                                            : pick_learn<false, false, false, false>(ts));
+    // the hard copy wins over the soft rule (dqn_agent.py:372-377).  A soft learn
+    // runs fused (TGT_SOFT) or as the plain kernel followed by k_target_soft --
+    // the same bits: without the shadow there is no soft instantiation, and
+    // below SOFT_FUSED_MIN_NA agents the two launches measured faster (the few
+    // workgroups reach their Adam epilogues together, nothing overlaps the
+    // extra target traffic, and the flat kernel streams it at full width)
+    const bool soft = !a->sync_target && a->tau > 0.0f;
+    const int path = option(DMDQN_OPT_SOFT_PATH);
+    const bool fuse = ts && (path == 1 || (path == 0 && a->NA >= SOFT_FUSED_MIN_NA));
+    const int tm = a->sync_target ? TGT_HARD : soft && fuse ? TGT_SOFT : TGT_NONE;
+    auto kern = a->qstats ? pick_learn_tm<true, false>(tm, ts) : pick_learn_tm<false, false>(tm, ts);
     if (a->row_format == DMDQN_ROWS_F32)  // float rows (the drop-in surface): X from a.xs / a.xn
-        kern = a->qstats ? (a->sync_target ? pick_learn<true, true, false, true>(ts)
-                                           : pick_learn<true, false, false, true>(ts))
-                         : (a->sync_target ? pick_learn<false, true, false, true>(ts)
-                                           : pick_learn<false, false, false, true>(ts));
+        kern = a->qstats ? pick_learn_tm<true, true>(tm, ts) : pick_learn_tm<false, true>(tm, ts);
     hipLaunchKernelGGL(kern, dim3(a->NA), dim3(512), 0, s, *a, (float *)nullptr);
     DMDQN_LAUNCH_CHECK("k_learn_" H16_NAME);
+    if (soft && !fuse)
+        return launch_target_soft(a->params, a->target, a->target_h, a->NA, a->P,
+                                  ts ? (a->P + 7) / 8 * 8 : a->P, a->precision, a->tau,
+                                  a->one_minus_tau, s);
     return DMDQN_OK;
 }
 
@@ -1283,25 +1378,23 @@ int H16_LAUNCH_GRAD(const dmdqn_learn_args *a, float *grad, hipStream_t s) {
     using namespace H16K;
     DMDQN_REQUIRE(a->row_format == DMDQN_ROWS_I8, "dmdqn_learn_grad: int8 replay rows only");
     const bool ts = a->target_h != nullptr;
-    auto kern = a->qstats ? pick_learn<true, false, true, false>(ts)
-                          : pick_learn<false, false, true, false>(ts);
+    auto kern = a->qstats ? pick_learn<true, TGT_NONE, true, false>(ts)
+                          : pick_learn<false, TGT_NONE, true, false>(ts);
     hipLaunchKernelGGL(kern, dim3(a->NA), dim3(512), 0, s, *a, grad);
     DMDQN_LAUNCH_CHECK("k_learn_" H16_NAME " (gradient)");
     return DMDQN_OK;
 }
 
-// The split learn's second launch (a's Adam constants and sync_target).
+// The split learn's second launch (a's Adam constants, sync_target and tau).
 int H16_LAUNCH_ADAM(const dmdqn_learn_args *a, const float *grad, hipStream_t s) {
     using namespace H16K;
     DMDQN_REQUIRE(a->P == L::P, "dmdqn_adam_agents: P=%d != %d", a->P, L::P);
     const dim3 grid((L::P / 4 + 255) / 256, a->NA);
     h16 *TH = reinterpret_cast<h16 *>(a->target_h);
-    if (a->sync_target)
-        hipLaunchKernelGGL(H16_ADAM_KERNEL<true>, grid, dim3(256), 0, s, a->params, a->adam_m,
-                           a->adam_v, a->target, TH, grad, a->alpha, a->c1, a->c2, a->eps);
-    else
-        hipLaunchKernelGGL(H16_ADAM_KERNEL<false>, grid, dim3(256), 0, s, a->params, a->adam_m,
-                           a->adam_v, a->target, TH, grad, a->alpha, a->c1, a->c2, a->eps);
+    auto kern = a->sync_target ? H16_ADAM_KERNEL<TGT_HARD>
+                : a->tau > 0.0f ? H16_ADAM_KERNEL<TGT_SOFT> : H16_ADAM_KERNEL<TGT_NONE>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, a->params, a->adam_m, a->adam_v, a->target, TH,
+                       grad, a->alpha, a->c1, a->c2, a->eps, a->tau, a->one_minus_tau);
     DMDQN_LAUNCH_CHECK("k_adam_agents_" H16_NAME);
     return DMDQN_OK;
 }

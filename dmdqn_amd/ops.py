@@ -28,7 +28,8 @@ ENTRY_POINTS = {
     "dmdqn_replay_store_f32": "replay_store_f32", "dmdqn_replay_gather_f32": "replay_gather_f32",
     "dmdqn_learn_shared_grad": "learn_shared_grad", "dmdqn_adam": "adam",
     "dmdqn_adam_slabs": "adam_slabs",
-    "dmdqn_target_sync": "target_sync", "dmdqn_q_argmax": "q_argmax",
+    "dmdqn_target_sync": "target_sync", "dmdqn_target_soft_update": "target_soft_update",
+    "dmdqn_q_argmax": "q_argmax",
     "dmdqn_q_argmax_shared": "q_argmax",
 }
 

@@ -373,12 +373,16 @@ void learn_step(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a
                 int64_t start, int64_t hidden, int64_t precision, bool sync, double gamma,
                 double alpha, double c1, double c2, double eps, int64_t loss_kind,
                 const OptT &qstats, const OptT &rn_out, const OptT &stamps, const OptT &grad,
-                const OptT &xs, const OptT &xn) {
+                const OptT &xs, const OptT &xn, double tau, double one_minus_tau) {
     const int64_t NA = loss.numel();
     dmdqn_learn_args a = make_learn(ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m,
                                     adam_v, target, target_h, loss, start, hidden, precision, sync,
                                     gamma, alpha, c1, c2, eps, loss_kind, qstats, rn_out,
                                     std::nullopt, stamps, NA, NA, xs, xn);
+    // the soft target update of this learn (update_target_network_soft,
+    // dqn_agent.py:389-399): float32(tau), float32(1 - tau) from the host; 0 = off
+    a.tau = (float)tau;
+    a.one_minus_tau = (float)one_minus_tau;
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
     if (grad.has_value()) {  // the split learn: gradient launch, then the Adam launch
         auto gr = dptr<float>(*grad, at::kFloat, "grad", NA * (int64_t)a.P);
@@ -463,6 +467,22 @@ void target_sync(const Tensor &params, Tensor &target, const OptT &target_h, int
           "dmdqn_target_sync");
 }
 
+void target_soft_update(const Tensor &params, Tensor &target, const OptT &target_h,
+                        int64_t precision, double tau, double one_minus_tau) {
+    TORCH_CHECK(params.dim() == 2, "params must be [NW, P]");
+    const int64_t NW = params.size(0), P = params.size(1);
+    auto p = dptr<float>(params, at::kFloat, "params");
+    auto t = dptr<float>(target, at::kFloat, "target", NW * P);
+    const int64_t Ph = target_h.has_value() ? target_h->numel() / NW : P;
+    TORCH_CHECK(!target_h.has_value() || (target_h->numel() % NW == 0 && Ph >= P),
+                "target_h must be [NW, Ph] with Ph >= P");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    check(dmdqn_target_soft_update(p, t, h16ptr(target_h, "target_h", precision), (int)NW, (int)P,
+                                   (int)Ph, (int)precision, (float)tau, (float)one_minus_tau,
+                                   stream_of(params)),
+          "dmdqn_target_soft_update");
+}
+
 void q_argmax(const Tensor &params, int64_t hidden, int64_t precision, const Tensor &obs,
               Tensor &out, const OptT &q, bool shared) {
     const int64_t NA = out.numel();
@@ -506,7 +526,7 @@ void learn_step_meta(const Tensor &, const Tensor &, const Tensor &, const Tenso
                      const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, const OptT &, Tensor &,
                      int64_t, int64_t, int64_t, bool, double, double, double, double, double,
                      int64_t, const OptT &, const OptT &, const OptT &, const OptT &, const OptT &,
-                     const OptT &) {}
+                     const OptT &, double, double) {}
 void learn_shared_grad_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                             const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                             const Tensor &, const Tensor &, Tensor &, int64_t, double, int64_t,
@@ -518,6 +538,7 @@ void adam_slabs_meta(Tensor &, Tensor &, Tensor &, Tensor &, const OptT &, const
 void adam_meta(Tensor &, Tensor &, Tensor &, Tensor &, const OptT &, const OptT &, const Tensor &,
                double, double, double, double, double, bool) {}
 void target_sync_meta(const Tensor &, Tensor &, const OptT &, int64_t) {}
+void target_soft_update_meta(const Tensor &, Tensor &, const OptT &, int64_t, double, double) {}
 void q_argmax_meta(const Tensor &, int64_t, int64_t, const Tensor &, Tensor &, const OptT &, bool) {}
 
 }  // namespace
@@ -571,7 +592,7 @@ TORCH_LIBRARY(dmdqn, m) {
           "Tensor(e!)? target_h, Tensor(f!) loss, int start, int hidden, int precision, bool sync, "
           "float gamma, float alpha, float c1, float c2, float eps, int loss_kind, "
           "Tensor(g!)? qstats, Tensor(h!)? rn_out, Tensor(i!)? stamps, Tensor(j!)? grad=None, "
-          "Tensor? xs=None, Tensor? xn=None) -> ()");
+          "Tensor? xs=None, Tensor? xn=None, float tau=0.0, float one_minus_tau=1.0) -> ()");
     // C5: per-agent gradients of one shared net, summed
     m.def("learn_shared_grad(Tensor ring_s, Tensor ring_n, Tensor ring_a, Tensor ring_d, "
           "Tensor ring_r, Tensor idx, Tensor params, Tensor target, Tensor target_h, "
@@ -588,6 +609,9 @@ TORCH_LIBRARY(dmdqn, m) {
           "float c1, float c2, float eps, bool sync) -> ()");
     // DQNAgent.update_target_network (dqn_agent.py:382-387)
     m.def("target_sync(Tensor params, Tensor(a!) target, Tensor(b!)? target_h, int precision) -> ()");
+    // DQNAgent.update_target_network_soft (dqn_agent.py:372-373, 389-399)
+    m.def("target_soft_update(Tensor params, Tensor(a!) target, Tensor(b!)? target_h, "
+          "int precision, float tau, float one_minus_tau) -> ()");
     // the greedy branch of select_action (dqn_agent.py:268-273)
     m.def("q_argmax(Tensor params, int hidden, int precision, Tensor obs, Tensor(a!) out, "
           "Tensor(b!)? q, bool shared) -> ()");
@@ -610,6 +634,7 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("adam", &adam);
     m.impl("adam_slabs", &adam_slabs);
     m.impl("target_sync", &target_sync);
+    m.impl("target_soft_update", &target_soft_update);
     m.impl("q_argmax", &q_argmax);
 }
 
@@ -630,5 +655,6 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("adam", &adam_meta);
     m.impl("adam_slabs", &adam_slabs_meta);
     m.impl("target_sync", &target_sync_meta);
+    m.impl("target_soft_update", &target_soft_update_meta);
     m.impl("q_argmax", &q_argmax_meta);
 }

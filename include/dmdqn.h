@@ -63,6 +63,9 @@ const char *dmdqn_last_error(void);
  * p) % (N + k), the next stores in the k slots no position maps to; the Python
  * ring uses k = 2 since round 6, k = 1 before), so a caller passes N + k; dmdqn_learn_shared_grad requires `work`; dmdqn_sim_step takes
  * action < 0 as "no setPhase".  1: cap = maxlen, work optional. */
+/* Since 4, additive (no version bump): dmdqn_learn_args ends with tau /
+ * one_minus_tau (zero = off, so a zero-initialised caller is unchanged) and
+ * dmdqn_target_soft_update is new -- the soft (Polyak) target update. */
 int dmdqn_version(void);
 
 /* The digest of the sources this library was built from (16 hex chars:
@@ -96,12 +99,20 @@ int dmdqn_debug_build(void);
  *   DMDQN_OPT_SAMPLE_TLOG (env DMDQN_SAMPLE_TLOG = n): cap the replay
  *     sampler's first-lane table at 2^n entries, 0 <= n <= 20 (forces
  *     collisions); 32 = no cap (default).
+ *   DMDQN_OPT_SOFT_PATH (env DMDQN_SOFT_PATH = fused | split): how a 16-bit
+ *     learn with dmdqn_learn_args.tau > 0 and a target shadow runs its soft
+ *     target update; 0 = auto (fused into the learn kernel's Adam epilogue from
+ *     2048 agents up, below that the plain learn followed by the
+ *     dmdqn_target_soft_update kernel on the same stream: the measured faster
+ *     of the two at each size), 1 = fused, 2 = the two launches.
+ *     The same bits either way.
  * dmdqn_set_option returns 0 or DMDQN_EINVAL (unknown option or value);
  * dmdqn_get_option returns the current value (DMDQN_EINVAL for an unknown
  * option).  Neither is synchronised with launches issued by other host
  * threads. */
 #define DMDQN_OPT_SIM_PATH 0
 #define DMDQN_OPT_SAMPLE_TLOG 1
+#define DMDQN_OPT_SOFT_PATH 2
 int dmdqn_set_option(int option, int value);
 int dmdqn_get_option(int option);
 
@@ -418,6 +429,26 @@ typedef struct dmdqn_learn_args {
                                         kernel reads them as f32.  Independent
                                         nets only (not the shared C5 learn).  */
     const float *xs, *xn;            /* DMDQN_ROWS_F32: [NA][batch][DMDQN_ROW_FLOATS] */
+    float tau, one_minus_tau;        /* soft (Polyak) target update after the Adam
+                                        step of this learn, the reference's
+                                        update_target_network_soft
+                                        (dqn_agent.py:372-373, 389-399):
+                                        target = fl32(fl32(tau * online) +
+                                        fl32(one_minus_tau * target)), three
+                                        rounded f32 ops, for all P parameters;
+                                        the 16-bit shadow is the RNE cast of the
+                                        new f32 target.  tau = 0 (default): off.
+                                        The host passes tau = float32(tau) and
+                                        one_minus_tau = float32(1.0 - tau), the
+                                        subtraction in double.  sync_target != 0
+                                        takes precedence (the reference's line
+                                        order, :372-377: the hard copy comes
+                                        last).  Honoured by dmdqn_learn and
+                                        dmdqn_adam_agents; ignored by
+                                        dmdqn_learn_grad and
+                                        dmdqn_learn_shared_grad.  Checked on the
+                                        host: tau finite in [0, 1] and, when
+                                        tau > 0, one_minus_tau in [0, 1].     */
 } dmdqn_learn_args;
 
 int dmdqn_learn(const dmdqn_learn_args *args, void *stream);
@@ -427,8 +458,8 @@ int dmdqn_learn(const dmdqn_learn_args *args, void *stream);
  * dmdqn_learn_grad runs the forward/backward and writes each agent's 16-bit
  * gradient (the values Keras's Adam receives, as f32) to grad [NA][P] (device
  * layout); dmdqn_adam_agents then applies the Keras-3 Adam step of the same
- * args (alpha, c1, c2, eps, sync_target) to params / adam_m / adam_v (and
- * target / target_h on a sync).  The second launch is bandwidth-bound and
+ * args (alpha, c1, c2, eps, sync_target, tau) to params / adam_m / adam_v (and
+ * target / target_h on a sync or a soft update).  The second launch is bandwidth-bound and
  * small-footprint, so the next env step's work can share the chip with it
  * (trainer.py, overlap "full").  grad is scratch owned by the caller. */
 int dmdqn_learn_grad(const dmdqn_learn_args *args, float *grad, void *stream);
@@ -439,6 +470,21 @@ int dmdqn_adam_agents(const dmdqn_learn_args *args, const float *grad, void *str
  * NULL (precision 1 = f16, 2 = bf16) also its 16-bit shadow [NW][Ph], RNE. */
 int dmdqn_target_sync(const float *params, float *target, uint16_t *target_h, int NW, int P,
                       int Ph, int precision, void *stream);
+
+/* Soft (Polyak) target update outside a learn
+ * (DQNAgent.update_target_network_soft, dqn_agent.py:389-399; its call site in
+ * learn() is :372-373): for NW nets and every parameter i of each,
+ *     target[i] = fl32(fl32(tau * params[i]) + fl32(one_minus_tau * target[i]))
+ * -- three separately rounded f32 operations, as TF's elementwise kernels --
+ * and, when target_h is not NULL (precision 1 = f16, 2 = bf16), its 16-bit
+ * shadow [NW][Ph] as the RNE cast of the new value.  tau in (0, 1];
+ * one_minus_tau = float32(1.0 - tau) in [0, 1].  P a multiple of 4, Ph of 4
+ * (16-byte f32 / 8-byte 16-bit lane accesses); the arguments are otherwise
+ * checked as dmdqn_target_sync's.  A learn with dmdqn_learn_args.tau > 0 leaves
+ * the bits of the same learn with tau = 0 followed by this call. */
+int dmdqn_target_soft_update(const float *params, float *target, uint16_t *target_h, int NW,
+                             int P, int Ph, int precision, float tau, float one_minus_tau,
+                             void *stream);
 
 /* Greedy actions argmax_a Q_online(obs) for NA agents (dqn_agent.py:268-273,
  * first max on ties); obs f32 [NA][89]; out int32 [NA]; q_out (optional)

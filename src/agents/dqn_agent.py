@@ -106,6 +106,12 @@ class DQNAgent:
         self.epsilon, self.epsilon_min = cfg.epsilon_start, cfg.epsilon_min
         self.batch_size = cfg.batch_size
         self.target_update_frequency = cfg.target_update_frequency
+        # additive config key "tau": soft target updates (the reference's
+        # update_target_network_soft, :389-399, reads self.tau but never sets
+        # it).  With tau > 0 in the config every learn() applies the update,
+        # fused into the learn kernel (the commented call at :372-373); without
+        # the key the attribute is None until the caller assigns it.
+        self.tau = config.get("tau")
         self.device = torch.device(device)
         # Keras draws every model's initial weights from TF's global generator, so
         # agents start from different weights; here each agent's initial-weight
@@ -169,6 +175,14 @@ class DQNAgent:
 
     def update_target_network(self):
         self._core.update_target_network()
+
+    def update_target_network_soft(self):
+        """target <- tau * online + (1 - tau) * target with self.tau (:389-399)."""
+        if self.tau is None:
+            raise AttributeError(
+                "DQNAgent.tau is not set: pass 'tau' in the agent config or assign agent.tau "
+                "before calling update_target_network_soft() (the reference never sets it)")
+        self._core.update_target_network_soft(self.tau)
 
     def get_epsilon(self) -> float:
         return self.epsilon

@@ -93,11 +93,24 @@ def create_agents(tl_junctions, config=AGENT_CONFIG):
     return {j: DQNAgent(state_size=89, action_size=4, agent_id=j, config=config) for j in tl_junctions}
 
 
+def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG):
+    """AGENT_CONFIG with the target-network rule of --tau /
+    --target_update_frequency: soft updates (dqn_agent.py:372-373, 389-399) of
+    rate tau after every learn, hard syncs every target_update_frequency learns
+    (0 = never; None = the config's)."""
+    config = dict(config)
+    if tau:
+        config["tau"] = float(tau)
+    if target_update_frequency is not None:
+        config["target_update_frequency"] = int(target_update_frequency)
+    return config
+
+
 def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenario=None,
-                 save_dir=None):
+                 save_dir=None, tau=0.0, target_update_frequency=None):
     dqn_agent.seed(seed)
     env, tl_junctions = initialize_environment(rows, cols, seed, scenario=scenario)
-    agents = create_agents(tl_junctions)
+    agents = create_agents(tl_junctions, target_config(tau, target_update_frequency))
     assert len(agents) == env.R * env.C
     smooth_total = SmoothedValue(alpha=0.3)
     out = open(metrics, "w") if metrics else None
@@ -132,7 +145,7 @@ def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenar
 
 def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, scenario=None,
                   shared=False, save_dir=None, resume=None, log_every=20, loss="mse",
-                  actuated=False):
+                  actuated=False, tau=0.0, target_update_frequency=None):
     """E env replicas of the loop on the GPU.  The optional JSONL carries the
     reference's learn scalars (dqn_agent.py:361-370: loss, epsilon,
     q_values_mean / _std, action_distribution) and its per-step rewards with
@@ -140,7 +153,7 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     replicas, every `log_every` steps (each record syncs)."""
     from dmdqn_amd.agent import AgentConfig
     from dmdqn_amd.trainer import Trainer
-    cfg = AgentConfig.from_dict(AGENT_CONFIG)
+    cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency))
     cfg.precision, cfg.seed, cfg.shared_params, cfg.loss = precision, seed, shared, loss
     tr = Trainer(EnvConfig(rows=rows, cols=cols, num_envs=envs, seed=seed, scenario=scenario,
                            actuated=actuated), cfg)
@@ -204,6 +217,11 @@ def main():
                     help="batched only: mse (dqn_agent.py:352) or huber (experimental/agent.py:99)")
     ap.add_argument("--actuated", action="store_true",
                     help="batched only: SUMO's actuated gap-out on phase 0 (default fixed durations)")
+    ap.add_argument("--tau", type=float, default=0.0,
+                    help="soft target updates of this rate after every learn "
+                         "(dqn_agent.py:389-399); 0 = off (the reference's training path)")
+    ap.add_argument("--target_update_frequency", type=int, default=None,
+                    help="hard target sync every N learns (default 500, train.py:118); 0 = never")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO)
     rows, cols = (int(x) for x in args.grid.split("x"))
@@ -215,9 +233,10 @@ def main():
     if args.batched:
         train_batched(args.episodes, rows, cols, args.envs, args.precision, args.seed, args.metrics,
                       scenario, args.shared, args.save_dir, args.resume, args.log_every, args.loss,
-                      args.actuated)
+                      args.actuated, args.tau, args.target_update_frequency)
     else:
-        train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir)
+        train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir,
+                     args.tau, args.target_update_frequency)
 
 
 if __name__ == "__main__":
