@@ -15,8 +15,16 @@ Draw-order contract (bit-exact with the reference when E = 1 and the global
 streams are seeded with random.seed(s) / np.random.seed(s)): per env, agents
 in junction order draw from that env's numpy stream for act and from its
 CPython `random` stream for replay sampling.
+
+Hyperparameter sweeps: AgentConfig.sweep gives every env replica its own
+learning_rate / gamma / tau (a grid of variants, replica g runs variant g % G),
+carried to the kernels as per-agent device arrays (include/dmdqn.h
+dmdqn_agent_hparams).  A replica computes, bit for bit, what it computes in a
+run whose scalar config holds its variant's values.
 """
 import ctypes as C
+import itertools
+import math
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -43,6 +51,12 @@ class CLearn(C.Structure):
         ("xs", C.c_void_p), ("xn", C.c_void_p), ("tau", C.c_float), ("one_minus_tau", C.c_float)]
 
 
+class CHParams(C.Structure):
+    """include/dmdqn.h dmdqn_agent_hparams."""
+    _fields_ = [(n, C.c_void_p) for n in ["lr", "gamma", "tau", "one_minus_tau"]] + [
+        ("adam_s", C.c_float), ("adam_d", C.c_float)]
+
+
 # ctypes signatures of the learn entry points: the C-ABI tests call them
 # directly (c_learn_args); the product path goes through torch.ops.dmdqn
 _lib.register({
@@ -65,6 +79,11 @@ _lib.register({
                           C.c_void_p],
     "dmdqn_target_soft_update": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_float, C.c_float, C.c_void_p],
+    "dmdqn_learn_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p],
+    "dmdqn_learn_grad_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_void_p],
+    "dmdqn_adam_agents_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_void_p],
+    "dmdqn_target_soft_update_hp": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
 })
 
 PRECISIONS = {"fp32": 0, "fp16": 1, "bf16": 2}
@@ -172,12 +191,22 @@ def kernel_to_keras(flat, hidden):
     return np.concatenate(parts, axis=-1)
 
 
-def keras_adam_consts(t, lr, b1=0.9, b2=0.999, eps=1e-7):
-    """keras/src/optimizers/adam.py update_step constants for local step t (f32 ops)."""
+def keras_adam_factors(t, b1=0.9, b2=0.999):
+    """(s, d) = (sqrt(1 - b2^t), 1 - b1^t) as float32: the two factors of
+    keras/src/optimizers/adam.py update_step's step size that do not depend on
+    the learning rate, alpha = fl32(fl32(lr * s) / d).  The kernels form alpha
+    from them and a per-agent lr (dmdqn_agent_hparams.adam_s / .adam_d)."""
     f = np.float32
     b1p = np.power(f(b1), f(t), dtype=np.float32)
     b2p = np.power(f(b2), f(t), dtype=np.float32)
-    alpha = f(f(lr) * np.sqrt(f(1) - b2p, dtype=np.float32)) / f(f(1) - b1p)
+    return np.sqrt(f(1) - b2p, dtype=np.float32), f(f(1) - b1p)
+
+
+def keras_adam_consts(t, lr, b1=0.9, b2=0.999, eps=1e-7):
+    """keras/src/optimizers/adam.py update_step constants for local step t (f32 ops)."""
+    f = np.float32
+    s, d = keras_adam_factors(t, b1, b2)
+    alpha = f(f(lr) * s) / d
     return float(alpha), float(f(1 - b1)), float(f(1 - b2)), float(f(eps))
 
 
@@ -200,6 +229,54 @@ def check_tau(tau, allow_zero=True):
     if not (0.0 <= t <= 1.0) or (t == 0.0 and not allow_zero):
         raise ValueError(f"tau must be in {'[' if allow_zero else '('}0, 1], got {tau!r}")
     return t
+
+
+SWEEP_KEYS = ("learning_rate", "gamma", "tau")
+
+
+def sweep_variants(cfg):
+    """The variants of cfg.sweep: a list of {learning_rate, gamma, tau} dicts,
+    the grid product of the swept keys' lists in key insertion order (last key
+    fastest); a key absent from the sweep keeps cfg's scalar.  No sweep: the
+    one variant of the scalar config.  ValueError on an unknown key, an empty
+    list, a non-finite value, learning_rate <= 0, gamma outside [0, 1], tau
+    outside (0, 1] (hard-only and soft nets cannot share a launch, so a tau
+    sweep cannot include 0) or a sweep over shared parameters (one net has one
+    set of hyperparameters)."""
+    base = {k: float(getattr(cfg, k)) for k in SWEEP_KEYS}
+    sweep = cfg.sweep
+    if sweep is None:
+        return [base]
+    if not isinstance(sweep, dict):
+        raise ValueError(f"sweep must be a dict of lists, got {type(sweep).__name__}")
+    if cfg.shared_params:
+        raise ValueError("sweep needs independent networks: shared_params trains one net, "
+                         "which has one set of hyperparameters")
+    lists = []
+    for k, vals in sweep.items():
+        if k not in SWEEP_KEYS:
+            raise ValueError(f"sweep key {k!r}: only {', '.join(SWEEP_KEYS)} can be swept")
+        try:
+            vals = [float(v) for v in vals]
+        except (TypeError, ValueError):
+            raise ValueError(f"sweep[{k!r}] must be a list of numbers, got {vals!r}") from None
+        if not vals:
+            raise ValueError(f"sweep[{k!r}] is empty")
+        for v in vals:
+            ok = math.isfinite(v) and (v > 0.0 if k == "learning_rate" else
+                                       0.0 <= v <= 1.0 if k == "gamma" else 0.0 < v <= 1.0)
+            if not ok:
+                rng = {"learning_rate": "> 0", "gamma": "in [0, 1]", "tau": "in (0, 1]"}[k]
+                raise ValueError(f"sweep[{k!r}]: {v!r} must be finite and {rng}")
+        lists.append(vals)
+    return [dict(base, **dict(zip(sweep, combo))) for combo in itertools.product(*lists)]
+
+
+def variant_assignment(n_variants, num_envs, env_offset=0):
+    """int64 [num_envs]: replica with global index g = env_offset + e runs
+    variant g % G, so a rank of a sharded run holds the variants a
+    single-process run gives those replicas."""
+    return (np.arange(num_envs, dtype=np.int64) + int(env_offset)) % int(n_variants)
 
 
 def keras_initial_weights(rng, hidden, n_agents):
@@ -275,6 +352,12 @@ class AgentConfig:
     # target_update_frequency still runs when due and wins on that learn;
     # target_update_frequency 0 = never hard-sync.
     tau: float = 0.0
+    # hyperparameter sweep across env replicas (sweep_variants): e.g.
+    # {"learning_rate": [1e-4, 3e-4, 1e-3], "gamma": [0.95, 0.99]} is a grid of
+    # G = 6 variants (key order, last key fastest); env replica g trains all its
+    # agents with variant g % G.  Keys: learning_rate, gamma, tau; an absent key
+    # keeps the scalar above.  None = every replica runs the scalar config.
+    sweep: Optional[dict] = None
 
     @classmethod
     def from_dict(cls, d):
@@ -291,7 +374,13 @@ def _soft_after_shared(agent, sync):
 
 
 class BatchedDQN:
-    """E*A independent DQN agents (agent index = env * A + junction)."""
+    """E*A independent DQN agents (agent index = env * A + junction).
+
+    variant_of_env ([E] indices into sweep_variants(cfg)) says which variant of
+    cfg.sweep each replica trains with.  Any assignment is allowed; the
+    default is e % G, and a Trainer passes (env_offset + e) % G
+    (variant_assignment).  A checkpoint stores the assignment beside the
+    sweep and a resume under another one is refused."""
 
     # rotating per-step output buffers (loss, qstats, actions, idx; see
     # __init__): at least 3, and ring_spare + 2 -- under trainer overlap "env"
@@ -301,8 +390,16 @@ class BatchedDQN:
     OUT_BUFS = 3
 
     def __init__(self, num_envs, n_agents, cfg: AgentConfig = None, device="cuda",
-                 env_seeds=None, init_weights=None, streams=None):
+                 env_seeds=None, init_weights=None, streams=None, variant_of_env=None):
         self.cfg = cfg = cfg or AgentConfig()
+        # the sweep's variants and each replica's (refusals before any device work)
+        self.variants = sweep_variants(cfg)
+        if variant_of_env is None:
+            variant_of_env = variant_assignment(len(self.variants), num_envs)
+        voe = np.asarray(variant_of_env, dtype=np.int64).reshape(-1)
+        if voe.shape != (num_envs,) or (voe < 0).any() or (voe >= len(self.variants)).any():
+            raise ValueError(f"variant_of_env must hold {num_envs} indices in "
+                             f"[0, {len(self.variants)})")
         self._ops = _ops()
         H = cfg.nn_layers[0]
         if len(cfg.nn_layers) != 2 or cfg.nn_layers[1] != H or H not in (64, 128):
@@ -417,6 +514,31 @@ class BatchedDQN:
         # "adam_slabs" = one rank's fused slab reduction + Adam; "allreduce" =
         # k_reduce_slabs -> all-reduce over ranks -> k_adam(gscale = 1/world)
         self.shared_paths = {"adam_slabs": 0, "allreduce": 0}
+        # per-agent hyperparameters of a sweep: f32 [NA] device arrays (agent =
+        # env * A + junction; every agent of a replica has its variant), built
+        # once; None for a key that is not swept (the launch scalar is used)
+        self.variant_of_env = torch.as_tensor(voe)
+        self._variant_of_agent = self.variant_of_env.repeat_interleave(n_agents).to(dev)
+        self.hp_lr = self.hp_gamma = self.hp_tau = self.hp_omt = None
+        swept = cfg.sweep or {}
+        per_agent = np.repeat(voe, n_agents)
+
+        def column(values):
+            return torch.as_tensor(np.asarray(values, dtype=np.float32)[per_agent]).to(dev)
+        if "learning_rate" in swept:
+            self.hp_lr = column([v["learning_rate"] for v in self.variants])
+        if "gamma" in swept:
+            self.hp_gamma = column([v["gamma"] for v in self.variants])
+        if "tau" in swept:
+            consts = [soft_update_consts(v["tau"]) for v in self.variants]
+            self.hp_tau = column([c[0] for c in consts])
+            self.hp_omt = column([c[1] for c in consts])
+        self._last_factors = (1.0, 1.0)
+
+    @property
+    def swept(self):
+        """Whether any hyperparameter is per agent (the _hp entry points run)."""
+        return self.hp_lr is not None or self.hp_gamma is not None or self.hp_tau is not None
 
     def set_split_learn(self, on=True):
         """Run each independent-agent learn as two launches (dmdqn_learn_grad,
@@ -527,6 +649,9 @@ class BatchedDQN:
             K.replay_sample(self.py_state, self.A, n, cfg.batch_size, out=self.idx)
         self.learn_step_counter += 1
         alpha, c1, c2, eps = keras_adam_consts(self.learn_step_counter, cfg.learning_rate)
+        # a swept learning rate: the kernels form each agent's alpha from these
+        s, d = keras_adam_factors(self.learn_step_counter)
+        self._last_factors = (float(s), float(d))
         # target_update_frequency 0: never hard-sync (soft updates alone)
         sync = (cfg.target_update_frequency > 0
                 and self.learn_step_counter % cfg.target_update_frequency == 0)
@@ -571,13 +696,20 @@ class BatchedDQN:
 
             def sl(t):
                 return None if t is None else t[lo:hi]
-            self._ops.learn_step(sl(ring.s), sl(ring.n), sl(ring.a), sl(ring.d), sl(ring.r),
-                                 sl(self.idx), sl(self.params), sl(self.adam_m), sl(self.adam_v),
-                                 sl(self.target), sl(self.target_h), sl(self.loss), ring.start,
-                                 self.H, PRECISIONS[cfg.precision], sync, cfg.gamma, alpha, c1, c2,
-                                 eps, LOSSES[cfg.loss], sl(qstats), sl(self.rn_out),
-                                 sl(self.stamps), grad=sl(self._split_grad), xs=xs, xn=xn,
-                                 tau=float(tau_f), one_minus_tau=float(omt_f))
+            args = (sl(ring.s), sl(ring.n), sl(ring.a), sl(ring.d), sl(ring.r),
+                    sl(self.idx), sl(self.params), sl(self.adam_m), sl(self.adam_v),
+                    sl(self.target), sl(self.target_h), sl(self.loss), ring.start,
+                    self.H, PRECISIONS[cfg.precision], sync, cfg.gamma, alpha, c1, c2,
+                    eps, LOSSES[cfg.loss], sl(qstats), sl(self.rn_out), sl(self.stamps))
+            kw = dict(grad=sl(self._split_grad), xs=xs, xn=xn, tau=float(tau_f),
+                      one_minus_tau=float(omt_f))
+            if self.swept:  # the range's slice of the per-agent arrays, like every tensor
+                s, d = self._last_factors
+                self._ops.learn_step_hp(*args, **kw, lr=sl(self.hp_lr), gamma_a=sl(self.hp_gamma),
+                                        tau_a=sl(self.hp_tau), one_minus_tau_a=sl(self.hp_omt),
+                                        adam_s=s, adam_d=d)
+            else:
+                self._ops.learn_step(*args, **kw)
         if hook:
             hook(False)
         return self.loss
@@ -603,6 +735,14 @@ class BatchedDQN:
                       None if self._xn is None else self._xn.data_ptr(),
                       *soft_update_consts(cfg.tau))
 
+    def c_learn_hparams(self):
+        """The dmdqn_agent_hparams block of the last learn (ctypes), next to
+        c_learn_args(): the per-agent arrays of the sweep (NULL where a key is
+        not swept) and the Adam factors of that learn."""
+        s, d = self._last_factors
+        return CHParams(*[None if t is None else t.data_ptr()
+                          for t in [self.hp_lr, self.hp_gamma, self.hp_tau, self.hp_omt]], s, d)
+
     def presample(self, n, lds_budget=0):
         """Draw the next learn's replay indices now (ReplayBuffer.sample,
         dqn_agent.py:59-63) for a ring of n transitions, into the index buffer
@@ -622,18 +762,39 @@ class BatchedDQN:
         self._presampled = (n, buf)
         return True
 
-    def learn_metrics(self):
+    def learn_metrics(self, by_variant=False):
         """The scalars dqn_agent.py:361-370 logs, from the last learn(collect_stats=True):
         mean over agents of q_values_mean / q_values_std (population std over
         each batch's 128x4 online Q values), the action histogram summed over
-        agents, mean loss and epsilon.  Syncs."""
+        agents, mean loss and epsilon.  by_variant: a list with one such record
+        per sweep variant, reduced over the agents of the variant's replicas,
+        plus "variant" (its index), its learning_rate / gamma / tau and "envs"
+        (how many replicas run it; the scalars are None for a variant without
+        replicas).  Syncs."""
         qs = self.qstats.double()
         n = float(self.cfg.batch_size * N_ACTIONS)
         mean = qs[:, 0] / n
         std = (qs[:, 1] / n - mean * mean).clamp_min(0).sqrt()
-        return {"loss": float(self.loss.double().mean()), "epsilon": float(self.epsilon),
-                "q_values_mean": float(mean.mean()), "q_values_std": float(std.mean()),
-                "action_distribution": qs[:, 2:6].sum(0).round().long().tolist()}
+        loss = self.loss.double()
+
+        def record(sel):
+            return {"loss": float(loss[sel].mean()), "epsilon": float(self.epsilon),
+                    "q_values_mean": float(mean[sel].mean()),
+                    "q_values_std": float(std[sel].mean()),
+                    "action_distribution": qs[sel, 2:6].sum(0).round().long().tolist()}
+        if not by_variant:
+            return record(slice(None))
+        out = []
+        for i, v in enumerate(self.variants):
+            envs = int((self.variant_of_env == i).sum())
+            rec = dict(variant=i, **v, envs=envs)
+            if envs:
+                rec.update(record(self._variant_of_agent == i))
+            else:
+                rec.update(loss=None, epsilon=float(self.epsilon), q_values_mean=None,
+                           q_values_std=None, action_distribution=[0] * N_ACTIONS)
+            out.append(rec)
+        return out
 
     def _learn_shared(self, alpha, c1, c2, eps, sync, qstats):
         """C5: grad = mean over this rank's agents of the per-agent gradients,
@@ -698,7 +859,13 @@ class BatchedDQN:
     def update_target_network_soft(self, tau=None):
         """dqn_agent.py:389-399 outside a learn: target <- tau * online +
         (1 - tau) * target for every net (three rounded f32 ops per parameter),
-        and the 16-bit shadow.  tau: cfg.tau by default; must be in (0, 1]."""
+        and the 16-bit shadow.  tau: cfg.tau by default (each net its own
+        under a tau sweep); must be in (0, 1]."""
+        if tau is None and self.hp_tau is not None:
+            self._ops.target_soft_update_hp(self.params, self.target, self.target_h,
+                                            PRECISIONS[self.cfg.precision], self.hp_tau,
+                                            self.hp_omt)
+            return
         tau_f, omt_f = soft_update_consts(
             check_tau(self.cfg.tau if tau is None else tau, allow_zero=False))
         self._ops.target_soft_update(self.params, self.target, self.target_h,

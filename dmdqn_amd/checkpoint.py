@@ -42,15 +42,17 @@ _AGENT_TENSORS = ["params", "target", "adam_m", "adam_v", "np_state", "py_state"
 # derived state stale), so load() refuses it.
 _AGENT_FIXED = ["precision", "shared_params", "nn_layers", "replay_buffer_size", "batch_size",
                 "seed", "loss", "target_update_frequency", "count_env_steps", "replay_rows",
-                "ring_spare", "tau"]
+                "ring_spare", "tau", "sweep"]
 _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features", "cap_lane",
               "end_ms", "period_ms", "step_duration", "max_sim_time", "action_stride", "scenario",
               "actuated"]
 # fields added after format 4 was introduced
 # (tau: the soft target update's rate; a checkpoint saved before it existed
-# ran hard updates only)
+# ran hard updates only.  sweep: per-replica hyperparameters; the per-agent
+# arrays are rebuilt from it, not stored, so a resume under another sweep would
+# train the restored nets with other values)
 _DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2,
-             "tau": 0.0}
+             "tau": 0.0, "sweep": None}
 
 
 def _written(total, ring):
@@ -72,8 +74,13 @@ def _check_cfg(saved, cur, fields, what):
 
 def _cfg_dict(cfg):
     d = dataclasses.asdict(cfg)
-    return {k: (v if isinstance(v, (int, float, str, bool, type(None), list)) else str(v))
-            for k, v in d.items()}
+    out = {k: (v if isinstance(v, (int, float, str, bool, type(None), list)) else str(v))
+           for k, v in d.items()}
+    if isinstance(d.get("sweep"), dict):
+        # [[key, [values]], ...]: the key order is part of the grid (it decides
+        # which variant a replica runs), so it is compared too
+        out["sweep"] = [[str(k), [float(x) for x in v]] for k, v in d["sweep"].items()]
+    return out
 
 
 def trainer_state(tr, include_replay=True):
@@ -83,6 +90,9 @@ def trainer_state(tr, include_replay=True):
     st = {"format": FORMAT,
           "env_cfg": _cfg_dict(env.cfg), "agent_cfg": _cfg_dict(ag.cfg),
           "nveh": int(env.nveh),
+          # which variant of agent_cfg.sweep each replica runs: g % G under a
+          # Trainer, but a BatchedDQN takes any assignment
+          "variant_of_env": [int(x) for x in ag.variant_of_env],
           "counters": {"learn_step_counter": ag.learn_step_counter,
                        "global_step_count": ag.global_step_count,
                        "epsilon": float(ag.epsilon), "learn_launches": ag.learn_launches,
@@ -119,6 +129,11 @@ def load(path, tr):
     _check_cfg(st["env_cfg"], _cfg_dict(env.cfg), _ENV_FIXED, "env_cfg")
     if int(st["nveh"]) != int(env.nveh):
         raise ValueError("checkpoint demand does not match this env config (nveh differs)")
+    # (absent before sweeps existed: every replica ran the one variant)
+    voe = st.get("variant_of_env")
+    if voe is not None and [int(x) for x in voe] != [int(x) for x in ag.variant_of_env]:
+        raise ValueError(f"checkpoint sweep assignment variant_of_env={list(voe)} != "
+                         f"{[int(x) for x in ag.variant_of_env]} of this Trainer")
     if int(st["counters"]["ring_total"]) > 0 and "replay" not in st:
         raise ValueError("checkpoint was saved without its replay (include_replay=False) but its "
                          "rings hold transitions: a resume would train on empty rings")

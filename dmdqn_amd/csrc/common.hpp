@@ -312,6 +312,42 @@ __device__ __forceinline__ float soft_el(float w, float t, float tau, float omt)
     return mul_rn(tau, w) + mul_rn(omt, t);
 }
 
+// A workgroup-uniform float computed on the VALU, moved to an SGPR (so a
+// per-agent constant costs no VGPR over the kernel's lifetime).
+__device__ __forceinline__ float uniform_f32(float x) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
+}
+
+// Per-agent Adam step size from dmdqn_agent_hparams: alpha = fl32(fl32(lr * s)
+// / d), the operations of agent.keras_adam_consts on the host -- one rounded
+// multiply (mul_rn: no contraction), one correctly rounded divide (HIP's
+// default) -- so the agent gets the bits of a scalar launch with its lr.
+__device__ __forceinline__ float hp_alpha(const dmdqn_agent_hparams &hp, int agent) {
+    return uniform_f32(mul_rn(hp.lr[agent], hp.adam_s) / hp.adam_d);
+}
+
+// The per-agent hyperparameters of `agent` written over the launch scalars of
+// this workgroup's copy of the learn arguments, once at kernel entry (a null
+// array keeps the scalar).  Everything after reads `a` as a scalar launch does.
+__device__ __forceinline__ void hp_apply(dmdqn_learn_args &a, const dmdqn_agent_hparams &hp,
+                                         int agent) {
+    if (hp.lr) a.alpha = hp_alpha(hp, agent);
+    if (hp.gamma) a.gamma = hp.gamma[agent];
+    if (hp.tau) {
+        a.tau = hp.tau[agent];
+        a.one_minus_tau = hp.one_minus_tau[agent];
+    }
+}
+
+// Which launches take their per-agent (HP) instantiation.  A launch does so
+// only when the block holds an array its kernel consumes, so that a block of
+// null arrays, or one that is irrelevant to the kernel, runs the scalar code:
+// the fused learn consumes all of them, the gradient-only launch of the split
+// learn gamma alone (the TD target), its Adam launch lr and tau.
+inline bool hp_any(const dmdqn_agent_hparams &hp) { return hp.lr || hp.gamma || hp.tau; }
+inline bool hp_grad(const dmdqn_agent_hparams &hp) { return hp.gamma != nullptr; }
+inline bool hp_adam(const dmdqn_agent_hparams &hp) { return hp.lr || hp.tau; }
+
 __device__ __forceinline__ void loss_term(int kind, float diff, float inv_b, float &term,
                                           float &dq) {
     if (kind == DMDQN_LOSS_HUBER) {

@@ -92,7 +92,9 @@ __device__ __forceinline__ void dense_tile(const TX *X, int ldx, const float *WT
 
 // Full forward of one 128-row batch: H1, H2 (post-ReLU) in LDS, Q -> z3[128][4].
 // X: the f16 LDS image (int8 rows) or the f32 pre-gathered rows (float rows).
-template <int H, typename TX>
+// HP (unused here): the per-agent-hyperparameter kernels call their own copy, so
+// the inliner sees the scalar kernels' copy with the callers it always had.
+template <int H, typename TX, bool HP = false>
 __device__ void forward(const float *P, const TX *X, float *H1, float *H2, float *z3) {
     using L = Lay<H>;
     const int w = threadIdx.x >> 6;
@@ -147,8 +149,16 @@ __device__ __forceinline__ void adam_el(float *w, float *m, float *v, float *tgt
 
 // XF: float replay rows (DMDQN_ROWS_F32): X(S') / X(S) are read as f32 from the
 // pre-gathered a.xn / a.xs (global, batch order) instead of the f16 LDS image.
-template <int H, bool XF>
-__global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a) {
+// HP: per-agent hyperparameters (dmdqn_agent_hparams) replace the launch
+// scalars of this workgroup's agent at entry (hp_apply); the scalar
+// instantiations take an empty block in its place (no kernel argument: their
+// signature, and so their code, is that of a kernel without the feature).
+struct NoHp {};
+template <bool HP>
+using HpArg = typename std::conditional<HP, dmdqn_agent_hparams, NoHp>::type;
+
+template <int H, bool XF, bool HP = false>
+__global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a, HpArg<HP> hp) {
     using L = Lay<H>;
     __shared__ __attribute__((aligned(16))) char smem[L::LDS];
     _Float16 *XL = (_Float16 *)(smem + L::X_OFF);
@@ -160,6 +170,7 @@ __global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a) {
               (int *)(sc + 3072),    (float *)(sc + 3584), (int *)(sc + 4096),
               (float *)(sc + 4608),  (double *)(sc + 5120), (double *)(sc + 6144)};
     const int agent = blockIdx.x;
+    if constexpr (HP) hp_apply(a, hp, agent);
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     const size_t P = (size_t)a.P;
     float *Wp = a.params + agent * P, *Mp = a.adam_m + agent * P, *Vp = a.adam_v + agent * P;
@@ -253,9 +264,9 @@ __global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a) {
         X = XL;
     }
     // ---- P2: target forward on S' -> z3 ; P3: online forward on S' -> a*, y
-    forward<H>(a.target + agent * P, X, H1, H2, S.z3);
+    forward<H, TX, HP>(a.target + agent * P, X, H1, H2, S.z3);
     // online forward on S': layer 3 reads H2 only, so its Q goes to the H1 region
-    forward<H>(Wp, X, H1, H2, H1);
+    forward<H, TX, HP>(Wp, X, H1, H2, H1);
     if (tid < B_) {
         // y = r + (gamma (1 - d)) q_t, each op rounded as TF's (mul_rn: no fma)
         const float *qo = H1 + tid * NACT;
@@ -274,7 +285,7 @@ __global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a) {
         gather(a.ring_s);
         X = XL;
     }
-    forward<H>(Wp, X, H1, H2, S.z3);
+    forward<H, TX, HP>(Wp, X, H1, H2, S.z3);
     if (a.qstats) learn_qstats(a.qstats, agent, S.z3, S.act);
     float lsum = 0.0f;
     if (tid < B_) {
@@ -475,12 +486,17 @@ __global__ void __launch_bounds__(256) k_q_argmax(const float *params, size_t ps
     }
 }
 
-int launch_learn_f16(const dmdqn_learn_args *a, hipStream_t s);   // learn_f16.hip
-int launch_learn_bf16(const dmdqn_learn_args *a, hipStream_t s);  // learn_bf16.hip
-int launch_learn_grad_f16(const dmdqn_learn_args *a, float *grad, hipStream_t s);
-int launch_learn_grad_bf16(const dmdqn_learn_args *a, float *grad, hipStream_t s);
-int launch_adam_agents_f16(const dmdqn_learn_args *a, const float *grad, hipStream_t s);
-int launch_adam_agents_bf16(const dmdqn_learn_args *a, const float *grad, hipStream_t s);
+// learn_f16.hip / learn_bf16.hip; hp: never null (a block of null arrays = none)
+int launch_learn_f16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, hipStream_t s);
+int launch_learn_bf16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, hipStream_t s);
+int launch_learn_grad_f16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, float *grad,
+                          hipStream_t s);
+int launch_learn_grad_bf16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, float *grad,
+                           hipStream_t s);
+int launch_adam_agents_f16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp,
+                           const float *grad, hipStream_t s);
+int launch_adam_agents_bf16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp,
+                            const float *grad, hipStream_t s);
 int check_tau(const char *who, float tau, float omt, bool zero_ok);
 
 // Soft target update outside a learn (dqn_agent.py:389-399,
@@ -488,12 +504,19 @@ int check_tau(const char *who, float tau, float omt, bool zero_ok);
 // P parameters, and the 16-bit shadow (RNE cast of the new f32 target) when
 // target_h is given.  One lane per 4 consecutive parameters (16-byte f32
 // accesses, one 8-byte shadow store); P4 = P / 4 lanes per net, n4 = NW * P4.
-template <typename T16>
+// PN: one tau per net (dmdqn_target_soft_update_hp), tau_a / omt_a [NW] read by
+// the lane's net; otherwise the launch scalars.
+template <typename T16, bool PN = false>
 __global__ void __launch_bounds__(256) k_target_soft(const float *params, float *target,
                                                      T16 *target_h, int P4, int Ph, long n4,
-                                                     float tau, float omt) {
+                                                     float tau, float omt, const float *tau_a,
+                                                     const float *omt_a) {
     const long q = (long)blockIdx.x * 256 + threadIdx.x;
     if (q >= n4) return;
+    if constexpr (PN) {
+        tau = tau_a[q / P4];
+        omt = omt_a[q / P4];
+    }
     const float4 w = reinterpret_cast<const float4 *>(params)[q];
     float4 t = reinterpret_cast<const float4 *>(target)[q];
     t.x = soft_el(w.x, t.x, tau, omt);
@@ -513,16 +536,23 @@ __global__ void __launch_bounds__(256) k_target_soft(const float *params, float 
 // The launch behind dmdqn_target_soft_update; also the second launch of a
 // 16-bit soft learn that does not run fused (learn_h16.hpp: target_h == NULL,
 // or fewer agents than SOFT_FUSED_MIN_NA).
+// tau_a / omt_a: one tau per net ([NW], both or neither) in place of tau / omt.
 int launch_target_soft(const float *params, float *target, uint16_t *target_h, int NW, int P,
-                       int Ph, int precision, float tau, float omt, hipStream_t s) {
+                       int Ph, int precision, float tau, float omt, const float *tau_a,
+                       const float *omt_a, hipStream_t s) {
     const long n4 = (long)NW * (P / 4);
     const dim3 grid((unsigned)((n4 + 255) / 256));
-    if (precision == 2)
-        hipLaunchKernelGGL(k_target_soft<__bf16>, grid, dim3(256), 0, s, params, target,
-                           reinterpret_cast<__bf16 *>(target_h), P / 4, Ph, n4, tau, omt);
-    else
-        hipLaunchKernelGGL(k_target_soft<_Float16>, grid, dim3(256), 0, s, params, target,
-                           reinterpret_cast<_Float16 *>(target_h), P / 4, Ph, n4, tau, omt);
+    if (precision == 2) {
+        auto k = tau_a ? k_target_soft<__bf16, true> : k_target_soft<__bf16, false>;
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, s, params, target,
+                           reinterpret_cast<__bf16 *>(target_h), P / 4, Ph, n4, tau, omt, tau_a,
+                           omt_a);
+    } else {
+        auto k = tau_a ? k_target_soft<_Float16, true> : k_target_soft<_Float16, false>;
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, s, params, target,
+                           reinterpret_cast<_Float16 *>(target_h), P / 4, Ph, n4, tau, omt, tau_a,
+                           omt_a);
+    }
     DMDQN_LAUNCH_CHECK("k_target_soft");
     return DMDQN_OK;
 }
@@ -562,21 +592,52 @@ int dmdqn::check_tau(const char *who, float tau, float omt, bool zero_ok) {
     return DMDQN_OK;
 }
 
-extern "C" int dmdqn_learn(const dmdqn_learn_args *a, void *stream) {
-    DMDQN_REQUIRE(a, "dmdqn_learn: null args");
-    if (int rc = check_tau("dmdqn_learn", a->tau, a->one_minus_tau, true)) return rc;
-    if (int rc = check_learn_args(a)) return rc;
-    if (a->precision == 1) return launch_learn_f16(a, as_stream(stream));
-    if (a->precision == 2) return launch_learn_bf16(a, as_stream(stream));
+// The host checks of a dmdqn_agent_hparams block (include/dmdqn.h); *out: the
+// block the launchers receive, all-null for hp == NULL.  The negated
+// comparisons refuse a NaN.
+static int check_hparams(const char *who, const dmdqn_agent_hparams *hp, dmdqn_agent_hparams *out) {
+    *out = dmdqn_agent_hparams{};
+    if (!hp) return DMDQN_OK;
+    DMDQN_REQUIRE((hp->tau != nullptr) == (hp->one_minus_tau != nullptr),
+                  "%s: tau and one_minus_tau go together (tau=%p one_minus_tau=%p)", who,
+                  (const void *)hp->tau, (const void *)hp->one_minus_tau);
+    DMDQN_REQUIRE(!hp->lr || (hp->adam_s > 0.0f && hp->adam_s <= 1.0f && hp->adam_d > 0.0f &&
+                              hp->adam_d <= 1.0f),
+                  "%s: with lr, adam_s=%g and adam_d=%g must be in (0, 1]", who,
+                  (double)hp->adam_s, (double)hp->adam_d);
+    *out = *hp;
+    return DMDQN_OK;
+}
+
+template <int H>
+static void launch_learn_f32(const dmdqn_learn_args *a, const dmdqn_agent_hparams &hp,
+                             hipStream_t s) {
     const bool xf = a->row_format == DMDQN_ROWS_F32;
+    if (hp_any(hp)) {
+        auto k = xf ? k_learn_f32<H, true, true> : k_learn_f32<H, false, true>;
+        hipLaunchKernelGGL(k, dim3(a->NA), dim3(512), 0, s, *a, hp);
+    } else {
+        auto k = xf ? k_learn_f32<H, true> : k_learn_f32<H, false>;
+        hipLaunchKernelGGL(k, dim3(a->NA), dim3(512), 0, s, *a, NoHp{});
+    }
+}
+
+// dmdqn_learn / dmdqn_learn_hp (`who` names the entry point in messages)
+static int learn_entry(const char *who, const dmdqn_learn_args *a, const dmdqn_agent_hparams *hpp,
+                       void *stream) {
+    DMDQN_REQUIRE(a, "%s: null args", who);
+    dmdqn_agent_hparams hp;
+    if (int rc = check_hparams(who, hpp, &hp)) return rc;
+    if (int rc = check_tau(who, a->tau, a->one_minus_tau, true)) return rc;
+    if (int rc = check_learn_args(a)) return rc;
+    if (a->precision == 1) return launch_learn_f16(a, &hp, as_stream(stream));
+    if (a->precision == 2) return launch_learn_bf16(a, &hp, as_stream(stream));
     if (a->hidden == 128) {
         DMDQN_REQUIRE(a->P == Lay<128>::P, "dmdqn_learn: P=%d != %d", a->P, Lay<128>::P);
-        auto k = xf ? k_learn_f32<128, true> : k_learn_f32<128, false>;
-        hipLaunchKernelGGL(k, dim3(a->NA), dim3(512), 0, as_stream(stream), *a);
+        launch_learn_f32<128>(a, hp, as_stream(stream));
     } else if (a->hidden == 64) {
         DMDQN_REQUIRE(a->P == Lay<64>::P, "dmdqn_learn: P=%d != %d", a->P, Lay<64>::P);
-        auto k = xf ? k_learn_f32<64, true> : k_learn_f32<64, false>;
-        hipLaunchKernelGGL(k, dim3(a->NA), dim3(512), 0, as_stream(stream), *a);
+        launch_learn_f32<64>(a, hp, as_stream(stream));
     } else {
         DMDQN_REQUIRE(false, "dmdqn_learn: hidden must be 64 or 128 (got %d)", a->hidden);
     }
@@ -584,24 +645,56 @@ extern "C" int dmdqn_learn(const dmdqn_learn_args *a, void *stream) {
     return DMDQN_OK;
 }
 
-extern "C" int dmdqn_learn_grad(const dmdqn_learn_args *a, float *grad, void *stream) {
+extern "C" int dmdqn_learn(const dmdqn_learn_args *a, void *stream) {
+    return learn_entry("dmdqn_learn", a, nullptr, stream);
+}
+
+extern "C" int dmdqn_learn_hp(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp,
+                              void *stream) {
+    return learn_entry("dmdqn_learn_hp", a, hp, stream);
+}
+
+static int learn_grad_entry(const char *who, const dmdqn_learn_args *a,
+                            const dmdqn_agent_hparams *hpp, float *grad, void *stream) {
+    dmdqn_agent_hparams hp;
+    if (int rc = check_hparams(who, hpp, &hp)) return rc;
     if (int rc = check_learn_args(a)) return rc;
-    DMDQN_REQUIRE(grad, "dmdqn_learn_grad: null grad");
+    DMDQN_REQUIRE(grad, "%s: null grad", who);
     DMDQN_REQUIRE(a->precision == 1 || a->precision == 2,
-                  "dmdqn_learn_grad: precision %d (the split learn is fp16 / bf16 only)",
-                  a->precision);
-    return a->precision == 1 ? launch_learn_grad_f16(a, grad, as_stream(stream))
-                             : launch_learn_grad_bf16(a, grad, as_stream(stream));
+                  "%s: precision %d (the split learn is fp16 / bf16 only)", who, a->precision);
+    return a->precision == 1 ? launch_learn_grad_f16(a, &hp, grad, as_stream(stream))
+                             : launch_learn_grad_bf16(a, &hp, grad, as_stream(stream));
+}
+
+extern "C" int dmdqn_learn_grad(const dmdqn_learn_args *a, float *grad, void *stream) {
+    return learn_grad_entry("dmdqn_learn_grad", a, nullptr, grad, stream);
+}
+
+extern "C" int dmdqn_learn_grad_hp(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp,
+                                   float *grad, void *stream) {
+    return learn_grad_entry("dmdqn_learn_grad_hp", a, hp, grad, stream);
+}
+
+static int adam_agents_entry(const char *who, const dmdqn_learn_args *a,
+                             const dmdqn_agent_hparams *hpp, const float *grad, void *stream) {
+    dmdqn_agent_hparams hp;
+    if (int rc = check_hparams(who, hpp, &hp)) return rc;
+    DMDQN_REQUIRE(a && grad && a->NA > 0 && a->params && a->adam_m && a->adam_v && a->target,
+                  "%s: null argument", who);
+    DMDQN_REQUIRE(a->precision == 1 || a->precision == 2, "%s: precision %d (fp16 / bf16 only)",
+                  who, a->precision);
+    if (int rc = check_tau(who, a->tau, a->one_minus_tau, true)) return rc;
+    return a->precision == 1 ? launch_adam_agents_f16(a, &hp, grad, as_stream(stream))
+                             : launch_adam_agents_bf16(a, &hp, grad, as_stream(stream));
 }
 
 extern "C" int dmdqn_adam_agents(const dmdqn_learn_args *a, const float *grad, void *stream) {
-    DMDQN_REQUIRE(a && grad && a->NA > 0 && a->params && a->adam_m && a->adam_v && a->target,
-                  "dmdqn_adam_agents: null argument");
-    DMDQN_REQUIRE(a->precision == 1 || a->precision == 2,
-                  "dmdqn_adam_agents: precision %d (fp16 / bf16 only)", a->precision);
-    if (int rc = check_tau("dmdqn_adam_agents", a->tau, a->one_minus_tau, true)) return rc;
-    return a->precision == 1 ? launch_adam_agents_f16(a, grad, as_stream(stream))
-                             : launch_adam_agents_bf16(a, grad, as_stream(stream));
+    return adam_agents_entry("dmdqn_adam_agents", a, nullptr, grad, stream);
+}
+
+extern "C" int dmdqn_adam_agents_hp(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp,
+                                    const float *grad, void *stream) {
+    return adam_agents_entry("dmdqn_adam_agents_hp", a, hp, grad, stream);
 }
 
 template <int H>
@@ -670,20 +763,38 @@ extern "C" int dmdqn_target_sync(const float *params, float *target, uint16_t *t
     return DMDQN_OK;
 }
 
+static int check_soft_update(const char *who, const float *params, const float *target,
+                             const uint16_t *target_h, int NW, int P, int Ph, int precision) {
+    DMDQN_REQUIRE(params && target && NW > 0 && P > 0 && Ph >= P, "%s: NW=%d P=%d Ph=%d", who, NW,
+                  P, Ph);
+    DMDQN_REQUIRE(precision >= 0 && precision <= 2, "%s: precision %d", who, precision);
+    DMDQN_REQUIRE(!target_h || precision != 0, "%s: fp32 has no 16-bit shadow", who);
+    DMDQN_REQUIRE(P % 4 == 0 && (!target_h || Ph % 4 == 0),
+                  "%s: P=%d and Ph=%d must be multiples of 4", who, P, Ph);
+    DMDQN_REQUIRE(((uintptr_t)params | (uintptr_t)target) % 16 == 0 && (uintptr_t)target_h % 8 == 0,
+                  "%s: params / target must be 16-byte aligned, target_h 8", who);
+    return DMDQN_OK;
+}
+
 extern "C" int dmdqn_target_soft_update(const float *params, float *target, uint16_t *target_h,
                                         int NW, int P, int Ph, int precision, float tau,
                                         float one_minus_tau, void *stream) {
-    DMDQN_REQUIRE(params && target && NW > 0 && P > 0 && Ph >= P,
-                  "dmdqn_target_soft_update: NW=%d P=%d Ph=%d", NW, P, Ph);
-    DMDQN_REQUIRE(precision >= 0 && precision <= 2, "dmdqn_target_soft_update: precision %d",
-                  precision);
-    DMDQN_REQUIRE(!target_h || precision != 0,
-                  "dmdqn_target_soft_update: fp32 has no 16-bit shadow");
-    DMDQN_REQUIRE(P % 4 == 0 && (!target_h || Ph % 4 == 0),
-                  "dmdqn_target_soft_update: P=%d and Ph=%d must be multiples of 4", P, Ph);
-    DMDQN_REQUIRE(((uintptr_t)params | (uintptr_t)target) % 16 == 0 && (uintptr_t)target_h % 8 == 0,
-                  "dmdqn_target_soft_update: params / target must be 16-byte aligned, target_h 8");
+    if (int rc = check_soft_update("dmdqn_target_soft_update", params, target, target_h, NW, P, Ph,
+                                   precision))
+        return rc;
     if (int rc = check_tau("dmdqn_target_soft_update", tau, one_minus_tau, false)) return rc;
     return launch_target_soft(params, target, target_h, NW, P, Ph, precision, tau, one_minus_tau,
-                              as_stream(stream));
+                              nullptr, nullptr, as_stream(stream));
+}
+
+extern "C" int dmdqn_target_soft_update_hp(const float *params, float *target, uint16_t *target_h,
+                                           int NW, int P, int Ph, int precision, const float *tau,
+                                           const float *one_minus_tau, void *stream) {
+    if (int rc = check_soft_update("dmdqn_target_soft_update_hp", params, target, target_h, NW, P,
+                                   Ph, precision))
+        return rc;
+    DMDQN_REQUIRE(tau && one_minus_tau,
+                  "dmdqn_target_soft_update_hp: tau and one_minus_tau arrays required");
+    return launch_target_soft(params, target, target_h, NW, P, Ph, precision, 0.0f, 0.0f, tau,
+                              one_minus_tau, as_stream(stream));
 }

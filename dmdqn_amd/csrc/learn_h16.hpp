@@ -1057,10 +1057,17 @@ __device__ __forceinline__ void bwd_dz1(h16 *R1, const uint32_t *mask, const f32
 // a compile-time choice, because a run-time branch between the two fragment
 // sources made the loaded registers meet at a control-flow merge, where the
 // compiler waits for every load (round 5).
-template <bool QSTATS, int TM, bool GOUT, bool XF = false, bool TS = true>
-__global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, float *gout) {
+// HP: per-agent hyperparameters (dmdqn_agent_hparams: lr, gamma, tau) replace
+// the launch scalars of this workgroup's agent once, at entry (hp_apply: scalar
+// loads and SGPR values, uniform per workgroup) -- a compile-time flag, so the
+// scalar instantiations never read hp and keep their code, and the Adam streams
+// of the per-agent ones carry no branch either.
+template <bool QSTATS, int TM, bool GOUT, bool XF = false, bool TS = true, bool HP = false>
+__global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, float *gout,
+                                                           dmdqn_agent_hparams hp) {
     LEARN_SMEM_SETUP;
     const int agent = blockIdx.x;
+    if constexpr (HP) hp_apply(a, hp, agent);
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, lr = l & 15, lg = l >> 4;
     const size_t Pz = (size_t)L::P;
     float *Wp = a.params + agent * Pz, *Mp = a.adam_m + agent * Pz, *Vp = a.adam_v + agent * Pz;
@@ -1270,15 +1277,23 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
 // arithmetic) on every agent's P parameters from grad[NA][P]; on a sync (TM =
 // TGT_HARD) or a soft update (TGT_SOFT, soft_el with the old target loaded
 // beside w, m, v) also the f32 target and its 16-bit shadow (agent stride Ph).
-// One lane per 4 consecutive parameters, blockIdx.y = agent.
-template <int TM>
+// One lane per 4 consecutive parameters, blockIdx.y = agent.  HP: the agent's
+// own alpha and tau from dmdqn_agent_hparams (as the learn kernel's hp_apply).
+template <int TM, bool HP = false>
 __global__ void __launch_bounds__(256) H16_ADAM_KERNEL(float *W, float *M, float *V, float *T,
                                                        h16 *TH, const float *G, float alpha,
                                                        float c1, float c2, float eps, float tau,
-                                                       float omt) {
+                                                       float omt, dmdqn_agent_hparams hp) {
     constexpr int P4 = L::P / 4;
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= P4) return;
+    if constexpr (HP) {
+        if (hp.lr) alpha = hp_alpha(hp, blockIdx.y);
+        if (TM == TGT_SOFT && hp.tau) {
+            tau = hp.tau[blockIdx.y];
+            omt = hp.one_minus_tau[blockIdx.y];
+        }
+    }
     const size_t Ph = ((size_t)L::P + 7) / 8 * 8;
     const size_t i = (size_t)blockIdx.y * L::P + 4 * (size_t)q;
     float4 w = *reinterpret_cast<const float4 *>(W + i), m = *reinterpret_cast<const float4 *>(M + i);
@@ -1319,30 +1334,43 @@ __global__ void __launch_bounds__(256) H16_ADAM_KERNEL(float *W, float *M, float
 
 DMDQN_DBG_READER(dbg_flags)
 
+using LearnKernel = void (*)(dmdqn_learn_args, float *, dmdqn_agent_hparams);
+
 // The kernel instance for a run-time target-shadow flag (TS above).
-template <bool QSTATS, int TM, bool GOUT, bool XF>
-void (*pick_learn(bool ts))(dmdqn_learn_args, float *) {
-    return ts ? H16_LEARN_KERNEL<QSTATS, TM, GOUT, XF, true>
-              : H16_LEARN_KERNEL<QSTATS, TM, GOUT, XF, false>;
+template <bool QSTATS, int TM, bool GOUT, bool XF, bool HP>
+LearnKernel pick_learn(bool ts) {
+    return ts ? H16_LEARN_KERNEL<QSTATS, TM, GOUT, XF, true, HP>
+              : H16_LEARN_KERNEL<QSTATS, TM, GOUT, XF, false, HP>;
 }
 
 // The fused learn's instance for a run-time target mode; TGT_SOFT exists with
 // the shadow only (the caller passes TGT_NONE otherwise).
-template <bool QSTATS, bool XF>
-void (*pick_learn_tm(int tm, bool ts))(dmdqn_learn_args, float *) {
-    if (tm == TGT_SOFT) return H16_LEARN_KERNEL<QSTATS, TGT_SOFT, false, XF, true>;
-    return tm == TGT_HARD ? pick_learn<QSTATS, TGT_HARD, false, XF>(ts)
-                          : pick_learn<QSTATS, TGT_NONE, false, XF>(ts);
+template <bool QSTATS, bool XF, bool HP>
+LearnKernel pick_learn_tm(int tm, bool ts) {
+    if (tm == TGT_SOFT) return H16_LEARN_KERNEL<QSTATS, TGT_SOFT, false, XF, true, HP>;
+    return tm == TGT_HARD ? pick_learn<QSTATS, TGT_HARD, false, XF, HP>(ts)
+                          : pick_learn<QSTATS, TGT_NONE, false, XF, HP>(ts);
+}
+
+// ... and for run-time metrics / float-row / per-agent-hyperparameter flags.
+template <bool HP>
+LearnKernel pick_learn_fused(bool qstats, bool xf, int tm, bool ts) {
+    if (xf)  // float rows (the drop-in surface): X from a.xs / a.xn
+        return qstats ? pick_learn_tm<true, true, HP>(tm, ts) : pick_learn_tm<false, true, HP>(tm, ts);
+    return qstats ? pick_learn_tm<true, false, HP>(tm, ts) : pick_learn_tm<false, false, HP>(tm, ts);
 }
 
 }  // namespace H16K
 
 int launch_target_soft(const float *params, float *target, uint16_t *target_h, int NW, int P,
-                       int Ph, int precision, float tau, float omt, hipStream_t s);  // learn.hip
+                       int Ph, int precision, float tau, float omt, const float *tau_a,
+                       const float *omt_a, hipStream_t s);  // learn.hip
 // DMDQN_OPT_SOFT_PATH auto: fuse the soft target update from this many agents up
 constexpr int SOFT_FUSED_MIN_NA = 2048;
 
-int H16_LAUNCH(const dmdqn_learn_args *a, hipStream_t s) {
+// hp: the per-agent hyperparameters, never null; a block of null arrays
+// launches the scalar kernels (every launcher below).
+int H16_LAUNCH(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, hipStream_t s) {
     DMDQN_REQUIRE(a->hidden == 128 && a->P == H16K::L::P,
                   "dmdqn_learn: precision %d (" H16_NAME ") needs hidden=128 (P=%d)", a->precision,
                   H16K::L::P);
@@ -1354,47 +1382,61 @@ int H16_LAUNCH(const dmdqn_learn_args *a, hipStream_t s) {
     // below SOFT_FUSED_MIN_NA agents the two launches measured faster (the few
     // workgroups reach their Adam epilogues together, nothing overlaps the
     // extra target traffic, and the flat kernel streams it at full width)
-    const bool soft = !a->sync_target && a->tau > 0.0f;
+    // (per-agent tau arrays make every learn a soft learn, values in (0, 1])
+    const bool soft = !a->sync_target && (a->tau > 0.0f || hp->tau);
     const int path = option(DMDQN_OPT_SOFT_PATH);
     const bool fuse = ts && (path == 1 || (path == 0 && a->NA >= SOFT_FUSED_MIN_NA));
     const int tm = a->sync_target ? TGT_HARD : soft && fuse ? TGT_SOFT : TGT_NONE;
-    auto kern = a->qstats ? pick_learn_tm<true, false>(tm, ts) : pick_learn_tm<false, false>(tm, ts);
-    if (a->row_format == DMDQN_ROWS_F32)  // float rows (the drop-in surface): X from a.xs / a.xn
-        kern = a->qstats ? pick_learn_tm<true, true>(tm, ts) : pick_learn_tm<false, true>(tm, ts);
-    hipLaunchKernelGGL(kern, dim3(a->NA), dim3(512), 0, s, *a, (float *)nullptr);
+    const bool xf = a->row_format == DMDQN_ROWS_F32;
+    auto kern = hp_any(*hp) ? pick_learn_fused<true>(a->qstats != nullptr, xf, tm, ts)
+                            : pick_learn_fused<false>(a->qstats != nullptr, xf, tm, ts);
+    hipLaunchKernelGGL(kern, dim3(a->NA), dim3(512), 0, s, *a, (float *)nullptr, *hp);
     DMDQN_LAUNCH_CHECK("k_learn_" H16_NAME);
     if (soft && !fuse)
         return launch_target_soft(a->params, a->target, a->target_h, a->NA, a->P,
                                   ts ? (a->P + 7) / 8 * 8 : a->P, a->precision, a->tau,
-                                  a->one_minus_tau, s);
+                                  a->one_minus_tau, hp->tau, hp->one_minus_tau, s);
     return DMDQN_OK;
 }
 
 // The split learn's first launch: forward/backward, gradient -> grad[NA][P].
-int H16_LAUNCH_GRAD(const dmdqn_learn_args *a, float *grad, hipStream_t s) {
+int H16_LAUNCH_GRAD(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, float *grad,
+                    hipStream_t s) {
     DMDQN_REQUIRE(a->hidden == 128 && a->P == H16K::L::P,
                   "dmdqn_learn_grad: precision %d (" H16_NAME ") needs hidden=128 (P=%d)",
                   a->precision, H16K::L::P);
     using namespace H16K;
     DMDQN_REQUIRE(a->row_format == DMDQN_ROWS_I8, "dmdqn_learn_grad: int8 replay rows only");
     const bool ts = a->target_h != nullptr;
-    auto kern = a->qstats ? pick_learn<true, TGT_NONE, true, false>(ts)
-                          : pick_learn<false, TGT_NONE, true, false>(ts);
-    hipLaunchKernelGGL(kern, dim3(a->NA), dim3(512), 0, s, *a, grad);
+    // the gradient depends on gamma alone (the TD target): common.hpp hp_grad
+    auto kern = hp_grad(*hp) ? (a->qstats ? pick_learn<true, TGT_NONE, true, false, true>(ts)
+                                       : pick_learn<false, TGT_NONE, true, false, true>(ts))
+                : a->qstats ? pick_learn<true, TGT_NONE, true, false, false>(ts)
+                            : pick_learn<false, TGT_NONE, true, false, false>(ts);
+    dmdqn_agent_hparams g{};
+    g.gamma = hp->gamma;
+    hipLaunchKernelGGL(kern, dim3(a->NA), dim3(512), 0, s, *a, grad, g);
     DMDQN_LAUNCH_CHECK("k_learn_" H16_NAME " (gradient)");
     return DMDQN_OK;
 }
 
 // The split learn's second launch (a's Adam constants, sync_target and tau).
-int H16_LAUNCH_ADAM(const dmdqn_learn_args *a, const float *grad, hipStream_t s) {
+int H16_LAUNCH_ADAM(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, const float *grad,
+                    hipStream_t s) {
     using namespace H16K;
     DMDQN_REQUIRE(a->P == L::P, "dmdqn_adam_agents: P=%d != %d", a->P, L::P);
     const dim3 grid((L::P / 4 + 255) / 256, a->NA);
     h16 *TH = reinterpret_cast<h16 *>(a->target_h);
-    auto kern = a->sync_target ? H16_ADAM_KERNEL<TGT_HARD>
-                : a->tau > 0.0f ? H16_ADAM_KERNEL<TGT_SOFT> : H16_ADAM_KERNEL<TGT_NONE>;
+    const int tm = a->sync_target ? TGT_HARD : (a->tau > 0.0f || hp->tau) ? TGT_SOFT : TGT_NONE;
+    auto kern = tm == TGT_HARD   ? H16_ADAM_KERNEL<TGT_HARD, false>
+                : tm == TGT_SOFT ? H16_ADAM_KERNEL<TGT_SOFT, false>
+                                 : H16_ADAM_KERNEL<TGT_NONE, false>;
+    if (hp_adam(*hp))  // gamma does not reach the optimizer
+        kern = tm == TGT_HARD   ? H16_ADAM_KERNEL<TGT_HARD, true>
+               : tm == TGT_SOFT ? H16_ADAM_KERNEL<TGT_SOFT, true>
+                                : H16_ADAM_KERNEL<TGT_NONE, true>;
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, a->params, a->adam_m, a->adam_v, a->target, TH,
-                       grad, a->alpha, a->c1, a->c2, a->eps, a->tau, a->one_minus_tau);
+                       grad, a->alpha, a->c1, a->c2, a->eps, a->tau, a->one_minus_tau, *hp);
     DMDQN_LAUNCH_CHECK("k_adam_agents_" H16_NAME);
     return DMDQN_OK;
 }

@@ -29,6 +29,9 @@ ENTRY_POINTS = {
     "dmdqn_learn_shared_grad": "learn_shared_grad", "dmdqn_adam": "adam",
     "dmdqn_adam_slabs": "adam_slabs",
     "dmdqn_target_sync": "target_sync", "dmdqn_target_soft_update": "target_soft_update",
+    "dmdqn_learn_hp": "learn_step_hp", "dmdqn_learn_grad_hp": "learn_step_hp",
+    "dmdqn_adam_agents_hp": "learn_step_hp",
+    "dmdqn_target_soft_update_hp": "target_soft_update_hp",
     "dmdqn_q_argmax": "q_argmax",
     "dmdqn_q_argmax_shared": "q_argmax",
 }

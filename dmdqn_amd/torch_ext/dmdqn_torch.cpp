@@ -393,6 +393,48 @@ void learn_step(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a
     check(dmdqn_learn(&a, stream_of(params)), "dmdqn_learn");
 }
 
+// learn_step with per-agent hyperparameters (include/dmdqn.h dmdqn_agent_hparams):
+// lr / gamma_a / tau_a / one_minus_tau_a f32 [NA] device tensors or None (the
+// scalar of the same launch), adam_s / adam_d the two Adam factors of this
+// learn as float32.  All None: exactly learn_step.
+void learn_step_hp(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
+                   const Tensor &ring_d, const Tensor &ring_r, const Tensor &idx, Tensor &params,
+                   Tensor &adam_m, Tensor &adam_v, Tensor &target, const OptT &target_h,
+                   Tensor &loss, int64_t start, int64_t hidden, int64_t precision, bool sync,
+                   double gamma, double alpha, double c1, double c2, double eps, int64_t loss_kind,
+                   const OptT &qstats, const OptT &rn_out, const OptT &stamps, const OptT &grad,
+                   const OptT &xs, const OptT &xn, double tau, double one_minus_tau,
+                   const OptT &lr, const OptT &gamma_a, const OptT &tau_a,
+                   const OptT &one_minus_tau_a, double adam_s, double adam_d) {
+    const int64_t NA = loss.numel();
+    dmdqn_learn_args a = make_learn(ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m,
+                                    adam_v, target, target_h, loss, start, hidden, precision, sync,
+                                    gamma, alpha, c1, c2, eps, loss_kind, qstats, rn_out,
+                                    std::nullopt, stamps, NA, NA, xs, xn);
+    a.tau = (float)tau;
+    a.one_minus_tau = (float)one_minus_tau;
+    dmdqn_agent_hparams hp{};
+    hp.lr = optr<const float>(lr, at::kFloat, "lr", NA);
+    hp.gamma = optr<const float>(gamma_a, at::kFloat, "gamma_a", NA);
+    hp.tau = optr<const float>(tau_a, at::kFloat, "tau_a", NA);
+    hp.one_minus_tau = optr<const float>(one_minus_tau_a, at::kFloat, "one_minus_tau_a", NA);
+    TORCH_CHECK((hp.tau == nullptr) == (hp.one_minus_tau == nullptr),
+                "tau_a and one_minus_tau_a go together");
+    for (const OptT *t : {&lr, &gamma_a, &tau_a, &one_minus_tau_a})
+        TORCH_CHECK(!t->has_value() || (*t)->device() == params.device(),
+                    "per-agent hyperparameters must be on the device of params");
+    hp.adam_s = (float)adam_s;
+    hp.adam_d = (float)adam_d;
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    if (grad.has_value()) {  // the split learn: gradient launch, then the Adam launch
+        auto gr = dptr<float>(*grad, at::kFloat, "grad", NA * (int64_t)a.P);
+        check(dmdqn_learn_grad_hp(&a, &hp, gr, stream_of(params)), "dmdqn_learn_grad_hp");
+        check(dmdqn_adam_agents_hp(&a, &hp, gr, stream_of(params)), "dmdqn_adam_agents_hp");
+        return;
+    }
+    check(dmdqn_learn_hp(&a, &hp, stream_of(params)), "dmdqn_learn_hp");
+}
+
 void learn_shared_grad(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
                        const Tensor &ring_d, const Tensor &ring_r, const Tensor &idx,
                        const Tensor &params, const Tensor &target, const Tensor &target_h,
@@ -483,6 +525,26 @@ void target_soft_update(const Tensor &params, Tensor &target, const OptT &target
           "dmdqn_target_soft_update");
 }
 
+// target_soft_update with one tau per net: tau / one_minus_tau f32 [NW].
+void target_soft_update_hp(const Tensor &params, Tensor &target, const OptT &target_h,
+                           int64_t precision, const Tensor &tau, const Tensor &one_minus_tau) {
+    TORCH_CHECK(params.dim() == 2, "params must be [NW, P]");
+    const int64_t NW = params.size(0), P = params.size(1);
+    auto p = dptr<float>(params, at::kFloat, "params");
+    auto t = dptr<float>(target, at::kFloat, "target", NW * P);
+    const int64_t Ph = target_h.has_value() ? target_h->numel() / NW : P;
+    TORCH_CHECK(!target_h.has_value() || (target_h->numel() % NW == 0 && Ph >= P),
+                "target_h must be [NW, Ph] with Ph >= P");
+    auto ta = dptr<const float>(tau, at::kFloat, "tau", NW);
+    auto oa = dptr<const float>(one_minus_tau, at::kFloat, "one_minus_tau", NW);
+    TORCH_CHECK(tau.device() == params.device() && one_minus_tau.device() == params.device(),
+                "tau / one_minus_tau must be on the device of params");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    check(dmdqn_target_soft_update_hp(p, t, h16ptr(target_h, "target_h", precision), (int)NW,
+                                      (int)P, (int)Ph, (int)precision, ta, oa, stream_of(params)),
+          "dmdqn_target_soft_update_hp");
+}
+
 void q_argmax(const Tensor &params, int64_t hidden, int64_t precision, const Tensor &obs,
               Tensor &out, const OptT &q, bool shared) {
     const int64_t NA = out.numel();
@@ -527,6 +589,12 @@ void learn_step_meta(const Tensor &, const Tensor &, const Tensor &, const Tenso
                      int64_t, int64_t, int64_t, bool, double, double, double, double, double,
                      int64_t, const OptT &, const OptT &, const OptT &, const OptT &, const OptT &,
                      const OptT &, double, double) {}
+void learn_step_hp_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                        const Tensor &, const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &,
+                        const OptT &, Tensor &, int64_t, int64_t, int64_t, bool, double, double,
+                        double, double, double, int64_t, const OptT &, const OptT &, const OptT &,
+                        const OptT &, const OptT &, const OptT &, double, double, const OptT &,
+                        const OptT &, const OptT &, const OptT &, double, double) {}
 void learn_shared_grad_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                             const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                             const Tensor &, const Tensor &, Tensor &, int64_t, double, int64_t,
@@ -539,6 +607,8 @@ void adam_meta(Tensor &, Tensor &, Tensor &, Tensor &, const OptT &, const OptT 
                double, double, double, double, double, bool) {}
 void target_sync_meta(const Tensor &, Tensor &, const OptT &, int64_t) {}
 void target_soft_update_meta(const Tensor &, Tensor &, const OptT &, int64_t, double, double) {}
+void target_soft_update_hp_meta(const Tensor &, Tensor &, const OptT &, int64_t, const Tensor &,
+                                const Tensor &) {}
 void q_argmax_meta(const Tensor &, int64_t, int64_t, const Tensor &, Tensor &, const OptT &, bool) {}
 
 }  // namespace
@@ -593,6 +663,16 @@ TORCH_LIBRARY(dmdqn, m) {
           "float gamma, float alpha, float c1, float c2, float eps, int loss_kind, "
           "Tensor(g!)? qstats, Tensor(h!)? rn_out, Tensor(i!)? stamps, Tensor(j!)? grad=None, "
           "Tensor? xs=None, Tensor? xn=None, float tau=0.0, float one_minus_tau=1.0) -> ()");
+    // DQNAgent.learn with per-agent learning_rate / gamma / tau (dqn_agent.py:112-113, :140,
+    // :347, :389-399: one config for every agent there, one value per agent here)
+    m.def("learn_step_hp(Tensor ring_s, Tensor ring_n, Tensor ring_a, Tensor ring_d, Tensor ring_r, "
+          "Tensor idx, Tensor(a!) params, Tensor(b!) adam_m, Tensor(c!) adam_v, Tensor(d!) target, "
+          "Tensor(e!)? target_h, Tensor(f!) loss, int start, int hidden, int precision, bool sync, "
+          "float gamma, float alpha, float c1, float c2, float eps, int loss_kind, "
+          "Tensor(g!)? qstats, Tensor(h!)? rn_out, Tensor(i!)? stamps, Tensor(j!)? grad=None, "
+          "Tensor? xs=None, Tensor? xn=None, float tau=0.0, float one_minus_tau=1.0, "
+          "Tensor? lr=None, Tensor? gamma_a=None, Tensor? tau_a=None, "
+          "Tensor? one_minus_tau_a=None, float adam_s=1.0, float adam_d=1.0) -> ()");
     // C5: per-agent gradients of one shared net, summed
     m.def("learn_shared_grad(Tensor ring_s, Tensor ring_n, Tensor ring_a, Tensor ring_d, "
           "Tensor ring_r, Tensor idx, Tensor params, Tensor target, Tensor target_h, "
@@ -612,6 +692,9 @@ TORCH_LIBRARY(dmdqn, m) {
     // DQNAgent.update_target_network_soft (dqn_agent.py:372-373, 389-399)
     m.def("target_soft_update(Tensor params, Tensor(a!) target, Tensor(b!)? target_h, "
           "int precision, float tau, float one_minus_tau) -> ()");
+    // update_target_network_soft with one tau per net
+    m.def("target_soft_update_hp(Tensor params, Tensor(a!) target, Tensor(b!)? target_h, "
+          "int precision, Tensor tau, Tensor one_minus_tau) -> ()");
     // the greedy branch of select_action (dqn_agent.py:268-273)
     m.def("q_argmax(Tensor params, int hidden, int precision, Tensor obs, Tensor(a!) out, "
           "Tensor(b!)? q, bool shared) -> ()");
@@ -630,11 +713,13 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("sim_step", &sim_step);
     m.impl("env_step", &env_step);
     m.impl("learn_step", &learn_step);
+    m.impl("learn_step_hp", &learn_step_hp);
     m.impl("learn_shared_grad", &learn_shared_grad);
     m.impl("adam", &adam);
     m.impl("adam_slabs", &adam_slabs);
     m.impl("target_sync", &target_sync);
     m.impl("target_soft_update", &target_soft_update);
+    m.impl("target_soft_update_hp", &target_soft_update_hp);
     m.impl("q_argmax", &q_argmax);
 }
 
@@ -651,10 +736,12 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("sim_step", &sim_step_meta);
     m.impl("env_step", &env_step_meta);
     m.impl("learn_step", &learn_step_meta);
+    m.impl("learn_step_hp", &learn_step_hp_meta);
     m.impl("learn_shared_grad", &learn_shared_grad_meta);
     m.impl("adam", &adam_meta);
     m.impl("adam_slabs", &adam_slabs_meta);
     m.impl("target_sync", &target_sync_meta);
     m.impl("target_soft_update", &target_soft_update_meta);
+    m.impl("target_soft_update_hp", &target_soft_update_hp_meta);
     m.impl("q_argmax", &q_argmax_meta);
 }

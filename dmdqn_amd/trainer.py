@@ -72,7 +72,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .agent import AgentConfig, BatchedDQN
+from .agent import AgentConfig, BatchedDQN, sweep_variants, variant_assignment
 from .env import EnvConfig, TrafficEnv
 
 
@@ -89,6 +89,11 @@ class Trainer:
     def __init__(self, env_cfg: EnvConfig = None, agent_cfg: AgentConfig = None, device="cuda",
                  overlap="none", side_stream=None, split_learn=False, fused=True,
                  war_events=True, side_learn=0, mark_every_learn=False):
+        # a sweep (AgentConfig.sweep) is checked before any device work, which
+        # starts with the env below; BatchedDQN, usable without a Trainer,
+        # expands the grid again for itself (host work on a few list entries)
+        agent_cfg = agent_cfg or AgentConfig()
+        n_variants = len(sweep_variants(agent_cfg))
         self.env = TrafficEnv(env_cfg or EnvConfig(), device=device)
         if overlap is True or overlap is False:
             overlap = "full" if overlap else "none"
@@ -104,8 +109,10 @@ class Trainer:
         self._side_pending = None  # overlap "env": the side learn, waited for lazily
         self._ev_env_prev = None  # overlap "learn": the last env step
         self._join = True  # the side stream's first work waits for everything before it
-        self.agent = BatchedDQN(self.env.E, self.env.A, agent_cfg or AgentConfig(), device=device,
-                                env_seeds=self.env.seeds)
+        # replica g = env_offset + e runs variant g % G of the sweep
+        voe = variant_assignment(n_variants, self.env.E, self.env.cfg.env_offset)
+        self.agent = BatchedDQN(self.env.E, self.env.A, agent_cfg, device=device,
+                                env_seeds=self.env.seeds, variant_of_env=voe)
         # overlap "learn": the sampler's LDS is what the shared learn's S' pass
         # leaves of a CU, so one sampler block runs beside each S' workgroup
         # (with the default four-blocks-per-CU budget the two serialise); the
@@ -459,6 +466,33 @@ class Trainer:
         self._side_pending = None
         if self.side is not None:
             torch.cuda.current_stream(self.env.device).wait_stream(self.side)
+
+    def variant_rewards(self):
+        """Per sweep variant, the mean over its replicas of the last step's
+        total reward (last_reward.sum(dim=1), train.py:254's sum over
+        junctions); None for a variant without replicas, [] before the first
+        step.  Syncs."""
+        if self.last_reward is None:
+            return []
+        total = self.last_reward.double().sum(dim=1).cpu()
+        voe = self.agent.variant_of_env
+        return [float(total[voe == i].mean()) if bool((voe == i).any()) else None
+                for i in range(len(self.agent.variants))]
+
+    def variant_rewards_device(self):
+        """variant_rewards() as a float64 [G] tensor on the device (NaN for a
+        variant without replicas), queued on the current stream: no copy to
+        the host and no sync, so a loop can accumulate it every step and read
+        it once.  The sums run in another order than variant_rewards()'s, so
+        the last bits may differ."""
+        if getattr(self, "_variant_weights", None) is None:
+            voe, G = self.agent.variant_of_env, len(self.agent.variants)
+            w = (voe[None, :] == torch.arange(G)[:, None]).double()  # [G, E] membership
+            n = w.sum(dim=1, keepdim=True)
+            w = torch.where(n > 0, w / n.clamp(min=1), torch.full_like(w, float("nan")))
+            self._variant_weights = w.to(self.env.device)
+        total = self.last_reward.double().sum(dim=1)
+        return (self._variant_weights * total[None, :]).sum(dim=1)
 
     def agent_env_steps(self, n_steps):
         return n_steps * self.env.E * self.env.A

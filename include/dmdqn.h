@@ -65,7 +65,11 @@ const char *dmdqn_last_error(void);
  * action < 0 as "no setPhase".  1: cap = maxlen, work optional. */
 /* Since 4, additive (no version bump): dmdqn_learn_args ends with tau /
  * one_minus_tau (zero = off, so a zero-initialised caller is unchanged) and
- * dmdqn_target_soft_update is new -- the soft (Polyak) target update. */
+ * dmdqn_target_soft_update is new -- the soft (Polyak) target update.
+ * dmdqn_agent_hparams with dmdqn_learn_hp, dmdqn_learn_grad_hp,
+ * dmdqn_adam_agents_hp and dmdqn_target_soft_update_hp are new -- per-agent
+ * learning rate, gamma and tau (a hyperparameter sweep across the env replicas
+ * of one run); dmdqn_learn_args and the entry points without _hp are unchanged. */
 int dmdqn_version(void);
 
 /* The digest of the sources this library was built from (16 hex chars:
@@ -485,6 +489,62 @@ int dmdqn_target_sync(const float *params, float *target, uint16_t *target_h, in
 int dmdqn_target_soft_update(const float *params, float *target, uint16_t *target_h, int NW,
                              int P, int Ph, int precision, float tau, float one_minus_tau,
                              void *stream);
+
+/* ------------------------------------------------------------------ per-agent hyperparameters
+ * The reference builds every DQNAgent of a run from one config
+ * (train.py:110-121 -> DQNAgent.__init__, dqn_agent.py:112-113, :140:
+ * learning_rate, gamma; tau: docs/improvements.md), so its agents differ by
+ * seed only.  Here each of the NA agents
+ * of a launch may carry its own values, read from optional device arrays
+ * indexed by the agent its workgroup serves -- one run is a whole sweep.  A
+ * NULL array keeps the launch scalar of dmdqn_learn_args.  Bit contract: agent
+ * i computes what a scalar launch with its values computes, operation for
+ * operation:
+ *   lr     the kernel forms alpha_i = fl32(fl32(lr[i] * adam_s) / adam_d), one
+ *          rounded multiply then one correctly rounded divide, no contraction
+ *          -- Keras-3 Adam's step size (keras/src/optimizers/adam.py
+ *          update_step; dqn_agent.py:357) as the host computes args->alpha;
+ *          c1, c2, eps stay launch scalars;
+ *   gamma  replaces args->gamma in y = r + gamma (1 - d) q_t (dqn_agent.py:347);
+ *   tau / one_minus_tau  given both or neither, every value in (0, 1] /
+ *          [0, 1), float32(tau) and float32(1.0 - tau) per element: they replace
+ *          args->tau / ->one_minus_tau in the soft target update
+ *          (dqn_agent.py:389-399).  When given, the learn is a soft learn
+ *          unless args->sync_target is set (the hard copy still wins,
+ *          :372-377).
+ * The arrays are device memory: their VALUES are the caller's to validate
+ * (the Python layer does, where it builds them); the host checks below cover
+ * the pointers and the two launch scalars. */
+typedef struct dmdqn_agent_hparams {
+    const float *lr;             /* [NA] or NULL: args->alpha is used            */
+    const float *gamma;          /* [NA] or NULL: args->gamma                    */
+    const float *tau;            /* [NA] or NULL (then args->tau); needs ...     */
+    const float *one_minus_tau;  /* ... this one too, and vice versa             */
+    float adam_s, adam_d;        /* with lr: sqrt(1-b2^t), 1-b1^t as float32     */
+} dmdqn_agent_hparams;
+
+/* dmdqn_learn / dmdqn_learn_grad / dmdqn_adam_agents (DQNAgent.learn,
+ * dqn_agent.py:328-380) with per-agent hyperparameters.  hp == NULL, or a block
+ * of NULL arrays, behaves exactly as the entry point without _hp (the same
+ * kernels are launched).  Refused on the host (DMDQN_EINVAL, before any
+ * launch): tau without one_minus_tau or the reverse; with lr, adam_s or adam_d
+ * not finite in (0, 1].  dmdqn_learn_grad_hp reads gamma only (the gradient
+ * launch has no Adam step and no target update); dmdqn_adam_agents_hp reads
+ * lr and tau / one_minus_tau. */
+int dmdqn_learn_hp(const dmdqn_learn_args *args, const dmdqn_agent_hparams *hp, void *stream);
+int dmdqn_learn_grad_hp(const dmdqn_learn_args *args, const dmdqn_agent_hparams *hp, float *grad,
+                        void *stream);
+int dmdqn_adam_agents_hp(const dmdqn_learn_args *args, const dmdqn_agent_hparams *hp,
+                         const float *grad, void *stream);
+
+/* dmdqn_target_soft_update (DQNAgent.update_target_network_soft,
+ * dqn_agent.py:389-399) with one tau per net: tau[NW], one_minus_tau[NW]
+ * (device, both required), net w updated with tau[w] / one_minus_tau[w] by the
+ * same three rounded f32 operations; everything else as
+ * dmdqn_target_soft_update. */
+int dmdqn_target_soft_update_hp(const float *params, float *target, uint16_t *target_h, int NW,
+                                int P, int Ph, int precision, const float *tau,
+                                const float *one_minus_tau, void *stream);
 
 /* Greedy actions argmax_a Q_online(obs) for NA agents (dqn_agent.py:268-273,
  * first max on ties); obs f32 [NA][89]; out int32 [NA]; q_out (optional)

@@ -13,6 +13,8 @@ stage for all agents (dmdqn_amd.trainer.Trainer) -- the throughput path.
 
   python -m src.scripts.train --episodes 2
   python -m src.scripts.train --batched --envs 1024 --grid 4x4 --episodes 1
+  python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 \
+      --sweep learning_rate=1e-4,5e-4,1e-3          # 3 variants in one run, ranked
 """
 import argparse
 import json
@@ -106,6 +108,28 @@ def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG):
     return config
 
 
+def parse_sweep(items):
+    """--sweep KEY=v1,v2,... (repeatable) -> AgentConfig.sweep: {key: [floats]}
+    in the order given (the grid's key order), or None for no items.  The keys
+    and values are checked where the sweep is used (agent.sweep_variants); here
+    only the syntax, and a key given twice."""
+    if not items:
+        return None
+    sweep = {}
+    for item in items:
+        key, sep, vals = str(item).partition("=")
+        key = key.strip()
+        if not sep or not key or not vals.strip():
+            raise ValueError(f"--sweep {item!r}: expected KEY=v1,v2,...")
+        if key in sweep:
+            raise ValueError(f"--sweep {key} given twice")
+        try:
+            sweep[key] = [float(v) for v in vals.split(",")]
+        except ValueError:
+            raise ValueError(f"--sweep {item!r}: values must be numbers") from None
+    return sweep
+
+
 def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenario=None,
                  save_dir=None, tau=0.0, target_update_frequency=None):
     dqn_agent.seed(seed)
@@ -145,16 +169,22 @@ def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenar
 
 def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, scenario=None,
                   shared=False, save_dir=None, resume=None, log_every=20, loss="mse",
-                  actuated=False, tau=0.0, target_update_frequency=None):
+                  actuated=False, tau=0.0, target_update_frequency=None, sweep=None):
     """E env replicas of the loop on the GPU.  The optional JSONL carries the
     reference's learn scalars (dqn_agent.py:361-370: loss, epsilon,
     q_values_mean / _std, action_distribution) and its per-step rewards with
     EMA smoothing (train.py:295-307, SmoothedValue alpha 0.3), averaged over
-    replicas, every `log_every` steps (each record syncs)."""
+    replicas, every `log_every` steps (each record syncs).  sweep
+    (AgentConfig.sweep, parse_sweep): replica g trains with variant g % G; each
+    record then carries "variants" (per variant: its hyperparameters, replicas,
+    total / smoothed total reward and learn scalars), the final line ranks the
+    variants by smoothed total reward, and the exported Keras weights are those
+    of the best variant's first replica (the checkpoint holds them all)."""
     from dmdqn_amd.agent import AgentConfig
     from dmdqn_amd.trainer import Trainer
     cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency))
     cfg.precision, cfg.seed, cfg.shared_params, cfg.loss = precision, seed, shared, loss
+    cfg.sweep = sweep
     tr = Trainer(EnvConfig(rows=rows, cols=cols, num_envs=envs, seed=seed, scenario=scenario,
                            actuated=actuated), cfg)
     from dmdqn_amd import checkpoint as CK
@@ -162,6 +192,8 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
         CK.load(resume, tr)
     out = open(metrics, "w") if metrics else None
     smooth_global, smooth_total = SmoothedValue(alpha=0.3), SmoothedValue(alpha=0.3)
+    variants = tr.agent.variants if sweep else []
+    smooth_variant = VariantSmoothedValues(alpha=0.3)
     t0 = time.perf_counter()
     steps = 0
     while tr.episode < episodes:
@@ -170,6 +202,9 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
             glob = -tr.env.local[..., :12].sum(dim=(1, 2), dtype=torch.float64)
         st = tr.step(collect_stats=log)
         steps += 1
+        if variants and (steps - 1) % log_every == 0:  # (the ranking needs no metrics file)
+            vr = tr.variant_rewards_device()  # stays on the device: no sync without a record
+            smooth_variant.update(vr)
         if log:
             total = tr.last_reward.sum(dim=1)                  # train.py:255 per replica
             g, tt = float(glob.mean()), float(total.mean())
@@ -180,18 +215,77 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
                    "smooth_total_reward": smooth_total.get_value()}
             if st.loss_launched:
                 rec.update(tr.agent.learn_metrics())
+            if variants:
+                if st.loss_launched:
+                    vrec = tr.agent.learn_metrics(by_variant=True)
+                else:
+                    voe = tr.agent.variant_of_env
+                    vrec = [dict(variant=i, **v, envs=int((voe == i).sum()))
+                            for i, v in enumerate(variants)]
+                for r, total_r, sm in zip(vrec, _host_values(vr), smooth_variant.get_values()):
+                    r.update(total_reward=total_r, smooth_total_reward=sm)
+                rec["variants"] = vrec
             out.write(json.dumps(rec) + "\n")
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    print(json.dumps({"agent_env_steps": steps * tr.env.E * tr.env.A, "seconds": round(el, 3),
-                      "agent_env_steps_per_s": round(steps * tr.env.E * tr.env.A / el, 1)}))
+    final = {"agent_env_steps": steps * tr.env.E * tr.env.A, "seconds": round(el, 3),
+             "agent_env_steps_per_s": round(steps * tr.env.E * tr.env.A / el, 1)}
+    best_env = 0
+    if variants:
+        final["variants"] = rank_variants(variants, tr.agent.variant_of_env.tolist(),
+                                          smooth_variant.get_values() or [None] * len(variants))
+        if final["variants"]:
+            best_env = final["variants"][0]["first_env"]
+    print(json.dumps(final))
     if out:
         out.close()
     if save_dir:
         os.makedirs(save_dir, exist_ok=True)
         CK.save(os.path.join(save_dir, "checkpoint.pt"), tr)
-        CK.export_keras_weights(tr.agent, save_dir, tr.env.grid.junction_ids, env_index=0)
+        CK.export_keras_weights(tr.agent, save_dir, tr.env.grid.junction_ids, env_index=best_env)
     return tr
+
+
+def _host_values(t):
+    """A float64 device vector as a list, None for NaN (a variant without
+    replicas).  Syncs."""
+    return [None if v != v else v for v in t.tolist()]
+
+
+class VariantSmoothedValues:
+    """One SmoothedValue per sweep variant, kept together as a float64 vector
+    on the device (SmoothedValue's rule, elementwise, in its order of
+    operations): update() queues device work only, get_values() copies to the
+    host and syncs -- once per metrics record and once at the end of the run."""
+
+    def __init__(self, alpha=0.5):
+        self.alpha = alpha
+        self.value = None
+
+    def update(self, new_val):
+        if self.value is None:
+            self.value = new_val
+        else:
+            self.value = self.alpha * new_val + (1 - self.alpha) * self.value
+
+    def get_values(self):
+        return [] if self.value is None else _host_values(self.value)
+
+
+def rank_variants(variants, variant_of_env, smoothed):
+    """The variants that have replicas, best smoothed total reward first (ties
+    and variants without a reward yet keep their grid order, after the others):
+    [{rank, variant, learning_rate, gamma, tau, envs, first_env,
+    smooth_total_reward}]."""
+    rows = []
+    for i, v in enumerate(variants):
+        envs = [e for e, k in enumerate(variant_of_env) if k == i]
+        if envs:
+            rows.append(dict(variant=i, **v, envs=len(envs), first_env=envs[0],
+                             smooth_total_reward=smoothed[i]))
+    rows.sort(key=lambda r: (r["smooth_total_reward"] is None,
+                             -(r["smooth_total_reward"] or 0.0), r["variant"]))
+    return [dict(rank=k + 1, **r) for k, r in enumerate(rows)]
 
 
 def main():
@@ -222,7 +316,17 @@ def main():
                          "(dqn_agent.py:389-399); 0 = off (the reference's training path)")
     ap.add_argument("--target_update_frequency", type=int, default=None,
                     help="hard target sync every N learns (default 500, train.py:118); 0 = never")
+    ap.add_argument("--sweep", action="append", default=None, metavar="KEY=v1,v2,...",
+                    help="batched only, repeatable: a hyperparameter sweep across the env "
+                         "replicas (KEY: learning_rate, gamma or tau); the variants are the grid "
+                         "of all --sweep lists, replica g runs variant g mod G")
     args = ap.parse_args()
+    try:
+        sweep = parse_sweep(args.sweep)
+    except ValueError as e:
+        ap.error(str(e))
+    if sweep and not args.batched:
+        ap.error("--sweep needs --batched")
     logging.basicConfig(level=logging.INFO)
     rows, cols = (int(x) for x in args.grid.split("x"))
     scenario = args.scenario
@@ -233,7 +337,7 @@ def main():
     if args.batched:
         train_batched(args.episodes, rows, cols, args.envs, args.precision, args.seed, args.metrics,
                       scenario, args.shared, args.save_dir, args.resume, args.log_every, args.loss,
-                      args.actuated, args.tau, args.target_update_frequency)
+                      args.actuated, args.tau, args.target_update_frequency, sweep)
     else:
         train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir,
                      args.tau, args.target_update_frequency)
