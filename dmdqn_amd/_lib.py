@@ -52,6 +52,21 @@ class DmdqnError(RuntimeError):
     pass
 
 
+NSTEP_MAX = 32  # include/dmdqn.h DMDQN_NSTEP_MAX
+
+
+class CNStep(C.Structure):
+    """include/dmdqn.h dmdqn_nstep_args (agent.CLearn / CHParams mirror the
+    learn's structs)."""
+    _fields_ = [(n, C.c_int32) for n in ["NA", "n", "head", "cap", "slot", "row_format"]] + [
+        (n, C.c_void_p) for n in ["st_s", "st_n", "st_a", "st_r", "st_d", "ring_s", "ring_n",
+                                  "ring_a", "ring_r", "ring_d"]] + [
+        ("gamma", C.c_double), ("gamma_a", C.c_void_p)]
+
+
+SIGNATURES["dmdqn_replay_nstep_commit"] = [C.POINTER(CNStep), vp]
+
+
 def register(sigs):
     """Add entry-point signatures (modules that define the ctypes structs call
     this); applied at once if the library is already loaded."""

@@ -21,6 +21,12 @@ learning_rate / gamma / tau (a grid of variants, replica g runs variant g % G),
 carried to the kernels as per-agent device arrays (include/dmdqn.h
 dmdqn_agent_hparams).  A replica computes, bit for bit, what it computes in a
 run whose scalar config holds its variant's values.
+
+n-step returns: with AgentConfig.n_step > 1, remember() (or a fused env step)
+writes the raw transition into a staging ring of n_step slots and one more
+launch (dmdqn_replay_nstep_commit) stores the n-step transition of the oldest
+staged one into the replay ring; the learn is unchanged and bootstraps with
+gamma^n_step, and its batch z-score runs over the stored returns.
 """
 import ctypes as C
 import itertools
@@ -233,6 +239,33 @@ def check_tau(tau, allow_zero=True):
 
 SWEEP_KEYS = ("learning_rate", "gamma", "tau")
 
+CNStep = _lib.CNStep  # include/dmdqn.h dmdqn_nstep_args
+NSTEP_MAX = _lib.NSTEP_MAX
+
+
+def check_n_step(n_step, replay_buffer_size):
+    """n_step as an int, or ValueError: an integer in 1..NSTEP_MAX, at most
+    replay_buffer_size (a window never outgrows the deque it feeds)."""
+    if isinstance(n_step, bool) or not isinstance(n_step, (int, np.integer)):
+        raise ValueError(f"n_step must be an integer in 1..{NSTEP_MAX}, got {n_step!r}")
+    n = int(n_step)
+    if not 1 <= n <= NSTEP_MAX:
+        raise ValueError(f"n_step must be in 1..{NSTEP_MAX}, got {n_step!r}")
+    if n > int(replay_buffer_size):
+        raise ValueError(f"n_step = {n} exceeds replay_buffer_size = {replay_buffer_size}")
+    return n
+
+
+def nstep_gamma(gamma, n_step):
+    """The bootstrap discount of an n-step transition, gamma^n as 1.0
+    multiplied n times by the Python float (n = 1: gamma exactly).  The learn
+    receives float32 of it in place of gamma (dqn_agent.py:347); a window cut
+    short by an episode end stores d = 1, which masks the bootstrap."""
+    G = 1.0
+    for _ in range(int(n_step)):
+        G = G * float(gamma)
+    return G
+
 
 def sweep_variants(cfg):
     """The variants of cfg.sweep: a list of {learning_rate, gamma, tau} dicts,
@@ -358,6 +391,16 @@ class AgentConfig:
     # agents with variant g % G.  Keys: learning_rate, gamma, tau; an absent key
     # keeps the scalar above.  None = every replica runs the scalar config.
     sweep: Optional[dict] = None
+    # n-step returns (docs/improvements.md item 7): every stored transition is
+    # (s_i, a_i, r_i + gamma r_{i+1} + ... , s'_{i+m-1}, d_{i+m-1}) over a window
+    # of up to n_step raw transitions, cut at an episode end, and the learn
+    # bootstraps with gamma^n_step.  The raw transitions pass through a staging
+    # ring of n_step slots (BatchedDQN.stage), so the transition that starts at
+    # raw store i is committed at raw store i + n_step - 1 and the last
+    # n_step - 1 raw transitions of a run are never committed.  1..32 and at
+    # most replay_buffer_size; 1 = the reference's one-step transitions (no
+    # staging ring, no extra launch).  Not a sweep key.
+    n_step: int = 1
 
     @classmethod
     def from_dict(cls, d):
@@ -394,6 +437,9 @@ class BatchedDQN:
         self.cfg = cfg = cfg or AgentConfig()
         # the sweep's variants and each replica's (refusals before any device work)
         self.variants = sweep_variants(cfg)
+        self.n_step = check_n_step(cfg.n_step, cfg.replay_buffer_size)
+        # what the learn takes for gamma: gamma^n_step (n_step 1: gamma itself)
+        self.gamma_n = nstep_gamma(cfg.gamma, self.n_step)
         if variant_of_env is None:
             variant_of_env = variant_assignment(len(self.variants), num_envs)
         voe = np.asarray(variant_of_env, dtype=np.int64).reshape(-1)
@@ -462,6 +508,20 @@ class BatchedDQN:
             raise ValueError("the shared-network learn reads int8 replay rows only")
         self.ring = K.ReplayRing(NA, cfg.replay_buffer_size, device=dev, row_format=cfg.replay_rows,
                                  spare=cfg.ring_spare)
+        # n_step > 1: the last n_step raw transitions of every agent, a replay
+        # ring of n_step slots that remember() / a fused env step write instead
+        # of self.ring; from the n_step-th raw store on, each raw store is
+        # followed by one commit of the window's oldest start into self.ring
+        # (commit_nstep).  store_ring is the ring raw stores go to.  The range
+        # flag of the staging ring's int8 stores is the main ring's (one pinned
+        # word), so ring.poll() / ring.check() cover both.
+        self.stage = None
+        if self.n_step > 1:
+            self.stage = K.ReplayRing(NA, self.n_step - 1, device=dev, spare=1,
+                                      row_format=cfg.replay_rows)
+            self.stage.err = self.ring.err
+        self.store_ring = self.ring if self.stage is None else self.stage
+        self.nstep_gamma_a = None  # f64 [NA]: the commit's per-agent gamma (a gamma sweep)
         self.OUT_BUFS = max(BatchedDQN.OUT_BUFS, self.ring.spare + 2)
         self._xs = self._xn = None  # float rows: the learn's pre-gathered batch
         if streams is not None:
@@ -528,7 +588,12 @@ class BatchedDQN:
         if "learning_rate" in swept:
             self.hp_lr = column([v["learning_rate"] for v in self.variants])
         if "gamma" in swept:
-            self.hp_gamma = column([v["gamma"] for v in self.variants])
+            # float32(gamma_v^n_step) for the learn; the n-step commit forms its
+            # returns with the variants' Python floats, in f64
+            self.hp_gamma = column([nstep_gamma(v["gamma"], self.n_step) for v in self.variants])
+            if self.stage is not None:
+                g64 = np.asarray([v["gamma"] for v in self.variants], dtype=np.float64)
+                self.nstep_gamma_a = torch.as_tensor(g64[per_agent]).to(dev)
         if "tau" in swept:
             consts = [soft_update_consts(v["tau"]) for v in self.variants]
             self.hp_tau = column([c[0] for c in consts])
@@ -595,11 +660,24 @@ class BatchedDQN:
 
     def remembered(self):
         """The bookkeeping of remember() after a fused env step stored the
-        transition into ring slot ring.next_slot."""
-        self.ring.advance()
+        transition into slot store_ring.next_slot of store_ring (self.ring, or
+        the n-step staging ring)."""
+        self.store_ring.advance()
+        self.commit_nstep()
         self.ring.poll()
         if self.cfg.count_env_steps:
             self.global_step_count += 1
+
+    def commit_nstep(self):
+        """n_step > 1, after a raw store into the staging ring: once it holds
+        n_step raw transitions, commit the n-step transition of the oldest one
+        into self.ring on the current stream (one launch) and advance it.  Raw
+        stores 0 .. n_step - 2 commit nothing.  A no-op for n_step = 1."""
+        st = self.stage
+        if st is not None and st.total >= st.slots:
+            # after the store the oldest raw transition sits in the slot the
+            # next store overwrites
+            self.ring.commit_nstep(st, st.next_slot, self.cfg.gamma, self.nstep_gamma_a)
 
     # -------------------------------------------------------------- replay
     def remember(self, obs, actions, rewards, next_obs, done):
@@ -610,8 +688,9 @@ class BatchedDQN:
             d = self._done_flags[int(bool(done))]  # constant [NA] u8 (no per-step fill)
         else:
             d = done.to(torch.uint8).reshape(self.E, 1).expand(self.E, self.A).reshape(NA).contiguous()
-        self.ring.store(obs.reshape(NA, D_IN), next_obs.reshape(NA, D_IN),
-                        actions.reshape(NA), rewards.reshape(NA), d)
+        self.store_ring.store(obs.reshape(NA, D_IN), next_obs.reshape(NA, D_IN),
+                              actions.reshape(NA), rewards.reshape(NA), d)
+        self.commit_nstep()
         self.ring.poll()  # raises (one store late, no stall) on a non-int8 observation
         if self.cfg.count_env_steps:
             self.global_step_count += 1
@@ -699,7 +778,7 @@ class BatchedDQN:
             args = (sl(ring.s), sl(ring.n), sl(ring.a), sl(ring.d), sl(ring.r),
                     sl(self.idx), sl(self.params), sl(self.adam_m), sl(self.adam_v),
                     sl(self.target), sl(self.target_h), sl(self.loss), ring.start,
-                    self.H, PRECISIONS[cfg.precision], sync, cfg.gamma, alpha, c1, c2,
+                    self.H, PRECISIONS[cfg.precision], sync, self.gamma_n, alpha, c1, c2,
                     eps, LOSSES[cfg.loss], sl(qstats), sl(self.rn_out), sl(self.stamps))
             kw = dict(grad=sl(self._split_grad), xs=xs, xn=xn, tau=float(tau_f),
                       one_minus_tau=float(omt_f))
@@ -725,7 +804,7 @@ class BatchedDQN:
                         for t in [self.ring.s, self.ring.n, self.ring.a, self.ring.d, self.ring.r,
                                   self.idx, self.params, self.adam_m, self.adam_v, self.target,
                                   self.target_h, self.loss]],
-                      np.float32(cfg.gamma), alpha, c1, c2, eps,
+                      np.float32(self.gamma_n), alpha, c1, c2, eps,
                       None if self.stamps is None else self.stamps.data_ptr(),
                       None if qstats is None else qstats.data_ptr(),
                       None if self.params_h is None else self.params_h.data_ptr(),
@@ -766,7 +845,8 @@ class BatchedDQN:
         """The scalars dqn_agent.py:361-370 logs, from the last learn(collect_stats=True):
         mean over agents of q_values_mean / q_values_std (population std over
         each batch's 128x4 online Q values), the action histogram summed over
-        agents, mean loss and epsilon.  by_variant: a list with one such record
+        agents, mean loss and epsilon, plus "n_step" (the config's: what the
+        loss and Q values were learned under).  by_variant: a list with one such record
         per sweep variant, reduced over the agents of the variant's replicas,
         plus "variant" (its index), its learning_rate / gamma / tau and "envs"
         (how many replicas run it; the scalars are None for a variant without
@@ -779,7 +859,7 @@ class BatchedDQN:
 
         def record(sel):
             return {"loss": float(loss[sel].mean()), "epsilon": float(self.epsilon),
-                    "q_values_mean": float(mean[sel].mean()),
+                    "n_step": self.n_step, "q_values_mean": float(mean[sel].mean()),
                     "q_values_std": float(std[sel].mean()),
                     "action_distribution": qs[sel, 2:6].sum(0).round().long().tolist()}
         if not by_variant:
@@ -791,7 +871,8 @@ class BatchedDQN:
             if envs:
                 rec.update(record(self._variant_of_agent == i))
             else:
-                rec.update(loss=None, epsilon=float(self.epsilon), q_values_mean=None,
+                rec.update(loss=None, epsilon=float(self.epsilon), n_step=self.n_step,
+                           q_values_mean=None,
                            q_values_std=None, action_distribution=[0] * N_ACTIONS)
             out.append(rec)
         return out
@@ -808,7 +889,8 @@ class BatchedDQN:
         # (dmdqn_adam_slabs, the same bits); more ranks: reduce, all-reduce, Adam
         self._ops.learn_shared_grad(ring.s, ring.n, ring.a, ring.d, ring.r, self.idx, self.params,
                                     self.target, self.target_h, self.params_h, self.loss,
-                                    ring.start, cfg.gamma, LOSSES[cfg.loss], qstats, self.rn_out,
+                                    ring.start, nstep_gamma(cfg.gamma, cfg.n_step),
+                                    LOSSES[cfg.loss], qstats, self.rn_out,
                                     self.slab, self.grad if world > 1 else None, 1.0 / self.NA,
                                     work=self.shared_work)
         if world == 1:

@@ -9,7 +9,8 @@ needs, so that load + K steps reproduces an uninterrupted run bit-exactly
 
   nets      params / target (+ its f16 / bf16 shadow) / Adam m, v, learn counters;
             the shared net's 16-bit online copy is rebuilt from params on load
-  replay    the filled part of every ring + the host counter
+  replay    the filled part of every ring + the host counter; with n_step > 1
+            also the staging ring of raw transitions and its counter ("nstep")
   streams   both device MT19937 streams per env (numpy act stream, CPython
             sample stream)
   env       lane rings, signal state, origin-queue cursors, stats, the clock,
@@ -42,7 +43,7 @@ _AGENT_TENSORS = ["params", "target", "adam_m", "adam_v", "np_state", "py_state"
 # derived state stale), so load() refuses it.
 _AGENT_FIXED = ["precision", "shared_params", "nn_layers", "replay_buffer_size", "batch_size",
                 "seed", "loss", "target_update_frequency", "count_env_steps", "replay_rows",
-                "ring_spare", "tau", "sweep"]
+                "ring_spare", "tau", "sweep", "n_step"]
 _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features", "cap_lane",
               "end_ms", "period_ms", "step_duration", "max_sim_time", "action_stride", "scenario",
               "actuated"]
@@ -50,9 +51,12 @@ _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features
 # (tau: the soft target update's rate; a checkpoint saved before it existed
 # ran hard updates only.  sweep: per-replica hyperparameters; the per-agent
 # arrays are rebuilt from it, not stored, so a resume under another sweep would
-# train the restored nets with other values)
+# train the restored nets with other values.  n_step: a checkpoint saved before
+# n-step returns existed stored one-step transitions; the rings of another
+# n_step hold other returns and the learn another discount)
 _DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2,
-             "tau": 0.0, "sweep": None}
+             "tau": 0.0, "sweep": None, "n_step": 1}
+_RING_TENSORS = ["s", "n", "a", "r", "d"]
 
 
 def _written(total, ring):
@@ -109,7 +113,12 @@ def trainer_state(tr, include_replay=True):
     st["obs"] = tr.obs.cpu()
     if include_replay:
         n = _written(ag.ring.total, ag.ring)
-        st["replay"] = {k: getattr(ag.ring, k)[:, :n].cpu() for k in ["s", "n", "a", "r", "d"]}
+        st["replay"] = {k: getattr(ag.ring, k)[:, :n].cpu() for k in _RING_TENSORS}
+    if ag.stage is not None:
+        # n_step > 1: the staging ring (the last n_step raw transitions, a
+        # window in flight) and its raw-store counter; n_step 1 adds no key
+        st["nstep"] = {k: getattr(ag.stage, k).cpu() for k in _RING_TENSORS}
+        st["nstep"]["total"] = int(ag.stage.total)
     return st
 
 
@@ -168,6 +177,13 @@ def load(path, tr):
                              f"{_written(int(c['ring_total']), ag.ring)}")
         for k, v in st["replay"].items():
             plan("replay", getattr(ag.ring, k)[:, :n], v, k)
+    # (n_step itself was compared above, so "nstep" is present exactly when
+    # this Trainer has a staging ring)
+    if (ag.stage is None) != ("nstep" not in st):
+        raise ValueError("checkpoint and Trainer disagree on the n-step staging ring")
+    if ag.stage is not None:
+        for k in _RING_TENSORS:
+            plan("nstep", getattr(ag.stage, k), st["nstep"][k], k)
     # the restore writes on the caller's stream: order it after everything the
     # trainer queued on its side stream (the "env" schedule's side learn may
     # still be updating its agents' weights and Adam slots -- ADVICE r5)
@@ -182,6 +198,8 @@ def load(path, tr):
     env.env_steps[:] = c["env_steps"]
     env.env_episodes[:] = c["env_episodes"]
     ag.ring.total = c["ring_total"]
+    if ag.stage is not None:
+        ag.stage.total = int(st["nstep"]["total"])
     ag._refresh_params_h()  # the 16-bit copies are derived from the f32 nets
     ag._refresh_target_h()
     tr.obs = st["obs"].to(env.device)

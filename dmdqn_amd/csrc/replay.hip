@@ -103,11 +103,106 @@ __global__ void k_replay_gather_f32(const float *rows_s, const float *rows_n, co
         reinterpret_cast<const float4 *>(rows_n + src)[grp];
 }
 
+// n-step returns (docs/improvements.md item 7): the transition of the window's
+// oldest raw transition, aggregated over up to n staged ones, written into the
+// replay ring in the row layout of k_replay_store / k_replay_store_f32.
+//
+// The staging arrays are a replay ring of n slots per agent (the same layout,
+// cap = n); the window is slots head, head+1, ... mod n, oldest first.  With
+//   m = the first j in 1..n whose done flag is set, or n
+//   R = r_0 + g r_1 + g^2 r_2 + ... + g^(m-1) r_(m-1)
+// (w = w * g, R = R + w * r_j: every product and sum one rounded f64 operation,
+// in that order) the committed transition is (s_0, a_0, R, s'_(m-1), d_(m-1)).
+//
+// One thread per (agent, 16-byte chunk of a row): CH chunks cover a row (8 for
+// int8 rows, 24 for float rows), each moved with one 16-byte load and store.
+// Every lane scans the n done bytes of its agent for m; the lane of chunk MC
+// forms R and writes the per-slot arrays -- for int8 rows MC is the chunk that
+// holds a, done and r (bytes 96..111 of the s' row), rewritten there.
+template <int ROW16, bool I8>
+__global__ void k_replay_nstep_commit(dmdqn_nstep_args a) {
+    constexpr int CH = ROW16;
+    constexpr int MC = I8 ? DMDQN_ROW_A / 16 : 0;
+    static_assert(!I8 || (DMDQN_ROW_A % 16 == 0 && DMDQN_ROW_R == DMDQN_ROW_A + 8),
+                  "a, done and r share one 16-byte chunk of the s' row");
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int agent = t / CH, ch = t - agent * CH;
+    if (agent >= a.NA) return;
+    const int n = a.n;
+    const size_t st0 = (size_t)agent * n;
+    // m - 1 = offset of the window's last entry; pos = its staging slot
+    int pos = a.head, last = n - 1;
+    for (int j = 0; j < n; j++) {
+        if (a.st_d[st0 + pos] != 0) {
+            last = j;
+            break;
+        }
+        if (j + 1 < n) pos = pos + 1 == n ? 0 : pos + 1;
+    }
+    const size_t src_s = (st0 + a.head) * CH + ch, src_n = (st0 + pos) * CH + ch;
+    const size_t row = (size_t)agent * a.cap + a.slot;
+    const uint4 vs = reinterpret_cast<const uint4 *>(a.st_s)[src_s];
+    uint4 vn = reinterpret_cast<const uint4 *>(a.st_n)[src_n];
+    if (ch == MC) {
+        const double g = a.gamma_a ? a.gamma_a[agent] : a.gamma;
+        double R = a.st_r[st0 + a.head], w = 1.0;
+        int p = a.head;
+        for (int j = 1; j <= last; j++) {
+            p = p + 1 == n ? 0 : p + 1;
+            w = __dmul_rn(w, g);
+            R = __dadd_rn(R, __dmul_rn(w, a.st_r[st0 + p]));
+        }
+        const uint8_t act = a.st_a[st0 + a.head];
+        const uint8_t done = a.st_d[st0 + pos] ? 1 : 0;
+        if (I8) {
+            const unsigned long long rb = __double_as_longlong(R);
+            vn = make_uint4((uint32_t)act | (uint32_t)done << 8, 0u, (uint32_t)rb,
+                            (uint32_t)(rb >> 32));
+        }
+        a.ring_a[row] = act;
+        a.ring_r[row] = R;
+        a.ring_d[row] = done;
+    }
+    reinterpret_cast<uint4 *>(a.ring_s)[row * CH + ch] = vs;
+    reinterpret_cast<uint4 *>(a.ring_n)[row * CH + ch] = vn;
+}
+
 DMDQN_DBG_READER(dbg_flags_replay)
 
 }  // namespace dmdqn
 
 using namespace dmdqn;
+
+extern "C" int dmdqn_replay_nstep_commit(const dmdqn_nstep_args *args, void *stream) {
+    DMDQN_REQUIRE(args, "dmdqn_replay_nstep_commit: null args");
+    const dmdqn_nstep_args &a = *args;
+    DMDQN_REQUIRE(a.n >= 1 && a.n <= DMDQN_NSTEP_MAX,
+                  "dmdqn_replay_nstep_commit: n=%d outside 1..%d", a.n, DMDQN_NSTEP_MAX);
+    DMDQN_REQUIRE(a.head >= 0 && a.head < a.n, "dmdqn_replay_nstep_commit: head=%d not in [0, %d)",
+                  a.head, a.n);
+    DMDQN_REQUIRE(a.NA > 0 && a.cap > 0 && a.slot >= 0 && a.slot < a.cap,
+                  "dmdqn_replay_nstep_commit: NA=%d cap=%d slot=%d", a.NA, a.cap, a.slot);
+    DMDQN_REQUIRE(a.row_format == DMDQN_ROWS_I8 || a.row_format == DMDQN_ROWS_F32,
+                  "dmdqn_replay_nstep_commit: unknown row_format %d", a.row_format);
+    DMDQN_REQUIRE(a.st_s && a.st_n && a.st_a && a.st_r && a.st_d && a.ring_s && a.ring_n &&
+                      a.ring_a && a.ring_r && a.ring_d,
+                  "dmdqn_replay_nstep_commit: null pointer");
+    DMDQN_REQUIRE(a.gamma_a || (a.gamma >= 0.0 && a.gamma <= 1.0),
+                  "dmdqn_replay_nstep_commit: gamma=%g must be finite in [0, 1]", a.gamma);
+    constexpr int CH8 = DMDQN_ROW_BYTES / 16, CH32 = DMDQN_ROW_FLOATS * 4 / 16;
+    static_assert(DMDQN_ROW_BYTES % 16 == 0 && (DMDQN_ROW_FLOATS * 4) % 16 == 0, "16-byte chunks");
+    const bool i8 = a.row_format == DMDQN_ROWS_I8;
+    const long long threads = (long long)a.NA * (i8 ? CH8 : CH32);
+    DMDQN_REQUIRE(threads <= 0x7fffffffLL, "dmdqn_replay_nstep_commit: NA=%d too large", a.NA);
+    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    if (i8)
+        hipLaunchKernelGGL((k_replay_nstep_commit<CH8, true>), grid, block, 0, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL((k_replay_nstep_commit<CH32, false>), grid, block, 0, as_stream(stream),
+                           a);
+    DMDQN_LAUNCH_CHECK("k_replay_nstep_commit");
+    return DMDQN_OK;
+}
 
 extern "C" int dmdqn_replay_store_f32(int NA, int cap, int slot, const float *obs_s,
                                       const float *obs_n, const int32_t *act, const double *rew,

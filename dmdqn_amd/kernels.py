@@ -174,6 +174,19 @@ class ReplayRing:
         a fused env step, env.TrafficEnv.step_fused)."""
         self.total += 1
 
+    def commit_nstep(self, stage, head, gamma, gamma_a=None):
+        """Store the n-step transition of the staging ring `stage` (a
+        ReplayRing of n = stage.slots slots, same row format; window = slots
+        head, head+1, ... mod n, oldest first) at slot next_slot and advance
+        (dmdqn_replay_nstep_commit, current stream).  gamma: the Python-float
+        discount of the return; gamma_a: f64 [NA] per-agent discounts instead."""
+        if stage.NA != self.NA or stage.row_format != self.row_format:
+            raise ValueError("the staging ring must have this ring's agents and row format")
+        _ops().replay_nstep_commit(int(head), self.next_slot, stage.s, stage.n, stage.a, stage.r,
+                                   stage.d, self.s, self.n, self.a, self.r, self.d, float(gamma),
+                                   gamma_a)
+        self.advance()
+
     def gather_f32(self, idx, xs, xn):
         """Float rows: the batch of deque positions idx [NA, batch] -> xs / xn
         [NA, batch, ROW_FLOATS] in batch order (the learn reads them there)."""

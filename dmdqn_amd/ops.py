@@ -26,6 +26,7 @@ ENTRY_POINTS = {
     "dmdqn_sim_step": "sim_step", "dmdqn_env_step": "env_step", "dmdqn_learn": "learn_step",
     "dmdqn_learn_grad": "learn_step", "dmdqn_adam_agents": "learn_step",
     "dmdqn_replay_store_f32": "replay_store_f32", "dmdqn_replay_gather_f32": "replay_gather_f32",
+    "dmdqn_replay_nstep_commit": "replay_nstep_commit",
     "dmdqn_learn_shared_grad": "learn_shared_grad", "dmdqn_adam": "adam",
     "dmdqn_adam_slabs": "adam_slabs",
     "dmdqn_target_sync": "target_sync", "dmdqn_target_soft_update": "target_soft_update",

@@ -193,6 +193,47 @@ void replay_gather_f32(const Tensor &rows_s, const Tensor &rows_n, const Tensor 
           "dmdqn_replay_gather_f32");
 }
 
+// The n-step transition of the staging window (include/dmdqn.h
+// dmdqn_replay_nstep_commit): st_* the staging ring [NA, n, ...], ring_* the
+// replay ring; int8 or float rows by the dtype of st_s; gamma_a f64 [NA] or None.
+void replay_nstep_commit(int64_t head, int64_t slot, const Tensor &st_s, const Tensor &st_n,
+                         const Tensor &st_a, const Tensor &st_r, const Tensor &st_d,
+                         Tensor &ring_s, Tensor &ring_n, Tensor &ring_a, Tensor &ring_r,
+                         Tensor &ring_d, double gamma, const OptT &gamma_a) {
+    TORCH_CHECK(st_a.dim() == 2 && ring_a.dim() == 2 && st_a.size(0) == ring_a.size(0),
+                "st_a must be [NA, n] and ring_a [NA, cap]");
+    const int64_t NA = st_a.size(0), n = st_a.size(1), cap = ring_a.size(1);
+    TORCH_CHECK(NA > 0 && n > 0 && cap > 0, "NA, n and cap must be positive");
+    TORCH_CHECK(st_s.scalar_type() == at::kChar || st_s.scalar_type() == at::kFloat,
+                "st_s must be int8 (128-byte rows) or float32 rows, got ", st_s.scalar_type());
+    const bool f32 = st_s.scalar_type() == at::kFloat;
+    const at::ScalarType rt = f32 ? at::kFloat : at::kChar;
+    const int64_t rw = f32 ? DMDQN_ROW_FLOATS : DMDQN_ROW_BYTES;
+    dmdqn_nstep_args a{};
+    a.NA = int32_of(NA, "NA"); a.n = int32_of(n, "n"); a.head = int32_of(head, "head");
+    a.cap = int32_of(cap, "cap"); a.slot = int32_of(slot, "slot");
+    a.row_format = f32 ? DMDQN_ROWS_F32 : DMDQN_ROWS_I8;
+    a.st_s = dptr<void>(st_s, rt, "st_s", NA * n * rw);
+    a.st_n = dptr<void>(st_n, rt, "st_n", NA * n * rw);
+    a.st_a = dptr<uint8_t>(st_a, at::kByte, "st_a", NA * n);
+    a.st_r = dptr<double>(st_r, at::kDouble, "st_r", NA * n);
+    a.st_d = dptr<uint8_t>(st_d, at::kByte, "st_d", NA * n);
+    a.ring_s = dptr<void>(ring_s, rt, "ring_s", NA * cap * rw);
+    a.ring_n = dptr<void>(ring_n, rt, "ring_n", NA * cap * rw);
+    a.ring_a = dptr<uint8_t>(ring_a, at::kByte, "ring_a", NA * cap);
+    a.ring_r = dptr<double>(ring_r, at::kDouble, "ring_r", NA * cap);
+    a.ring_d = dptr<uint8_t>(ring_d, at::kByte, "ring_d", NA * cap);
+    a.gamma = gamma;
+    a.gamma_a = optr<const double>(gamma_a, at::kDouble, "gamma_a", NA);
+    for (const Tensor *t : std::initializer_list<const Tensor *>{
+             &st_n, &st_a, &st_r, &st_d, &ring_s, &ring_n, &ring_a, &ring_r, &ring_d})
+        TORCH_CHECK(t->device() == st_s.device(), "staging and replay rings must share a device");
+    TORCH_CHECK(!gamma_a.has_value() || gamma_a->device() == st_s.device(),
+                "gamma_a must be on the device of the rings");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(st_s.device());
+    check(dmdqn_replay_nstep_commit(&a, stream_of(st_s)), "dmdqn_replay_nstep_commit");
+}
+
 void replay_sample(Tensor &py_state, int64_t A, int64_t n, int64_t k, Tensor &idx,
                    int64_t lds_budget) {
     const int64_t E = py_state.numel() / MT;
@@ -571,6 +612,9 @@ void observe_meta(int64_t, int64_t, const Tensor &, const Tensor &, const Tensor
 void replay_store_meta(int64_t, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                        const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, Tensor &) {}
 void replay_sample_meta(Tensor &, int64_t, int64_t, int64_t, Tensor &, int64_t) {}
+void replay_nstep_commit_meta(int64_t, int64_t, const Tensor &, const Tensor &, const Tensor &,
+                              const Tensor &, const Tensor &, Tensor &, Tensor &, Tensor &,
+                              Tensor &, Tensor &, double, const OptT &) {}
 void replay_store_f32_meta(int64_t, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                            const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, Tensor &) {}
 void replay_gather_f32_meta(const Tensor &, const Tensor &, const Tensor &, int64_t, Tensor &,
@@ -643,6 +687,11 @@ TORCH_LIBRARY(dmdqn, m) {
           "Tensor(e!) ring_d) -> ()");
     m.def("replay_gather_f32(Tensor rows_s, Tensor rows_n, Tensor idx, int start, Tensor(a!) xs, "
           "Tensor(b!) xn) -> ()");
+    // n-step returns built at the replay store (docs/improvements.md item 7; the reference
+    // stores one-step transitions, dqn_agent.py:31-57, for the target of :347)
+    m.def("replay_nstep_commit(int head, int slot, Tensor st_s, Tensor st_n, Tensor st_a, "
+          "Tensor st_r, Tensor st_d, Tensor(a!) ring_s, Tensor(b!) ring_n, Tensor(c!) ring_a, "
+          "Tensor(d!) ring_r, Tensor(e!) ring_d, float gamma, Tensor? gamma_a=None) -> ()");
     // traci.load (train.py:190); setPhase x A + simulationStep x K (train.py:225-236)
     m.def("sim_reset(Tensor(a!)[] state, Tensor[] tables, int[] dims, Tensor? mask=None) -> ()");
     m.def("sim_step(Tensor(a!)[] state, Tensor[] tables, int[] dims, float[] idm, Tensor? actions, "
@@ -709,6 +758,7 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("replay_sample", &replay_sample);
     m.impl("replay_store_f32", &replay_store_f32);
     m.impl("replay_gather_f32", &replay_gather_f32);
+    m.impl("replay_nstep_commit", &replay_nstep_commit);
     m.impl("sim_reset", &sim_reset);
     m.impl("sim_step", &sim_step);
     m.impl("env_step", &env_step);
@@ -732,6 +782,7 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("replay_sample", &replay_sample_meta);
     m.impl("replay_store_f32", &replay_store_f32_meta);
     m.impl("replay_gather_f32", &replay_gather_f32_meta);
+    m.impl("replay_nstep_commit", &replay_nstep_commit_meta);
     m.impl("sim_reset", &sim_reset_meta);
     m.impl("sim_step", &sim_step_meta);
     m.impl("env_step", &env_step_meta);

@@ -59,6 +59,13 @@ sequential order, so results are bit-identical (tests/test_gpu_overlap.py).
               side:  [wait env_step_{t-1}] sample_t (ev_s)
               main:  env_step_t [wait ev_s] learn_t
 
+n-step returns (AgentConfig.n_step > 1): the raw transition of a step goes to
+the agent's staging ring (agent.store_ring) and remember() / remembered()
+commit the window's oldest start into agent.ring on the same stream, so the
+ring a learn samples lags the raw stores by n_step - 1 steps.  "none" (fused
+and fused=False) and "env" (with and without side_learn) run it, bit-identical
+to each other; "sample", "learn" and "full" raise ValueError for n_step > 1.
+
 What a step returns or exposes per step (obs, reward, loss, agent.actions,
 agent.idx) is fresh or double-buffered, so the caller may read it on its own
 stream between steps (under "env" with side_learn, read the loss through
@@ -72,7 +79,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .agent import AgentConfig, BatchedDQN, sweep_variants, variant_assignment
+from .agent import AgentConfig, BatchedDQN, check_n_step, sweep_variants, variant_assignment
 from .env import EnvConfig, TrafficEnv
 
 
@@ -94,6 +101,15 @@ class Trainer:
         # expands the grid again for itself (host work on a few list entries)
         agent_cfg = agent_cfg or AgentConfig()
         n_variants = len(sweep_variants(agent_cfg))
+        # n-step returns (AgentConfig.n_step > 1) run under "none" (fused or
+        # not) and "env" (with or without side_learn), bit-identical to each
+        # other.  "sample", "learn" and "full" draw the next learn's indices
+        # before the store, for the ring length they predict from the raw store
+        # count; with a staging ring in between that prediction does not hold,
+        # so they are refused
+        if check_n_step(agent_cfg.n_step, agent_cfg.replay_buffer_size) > 1 and overlap in (
+                "sample", "learn", "full", True):
+            raise ValueError(f'n_step > 1 runs under overlap "none" or "env", not {overlap!r}')
         self.env = TrafficEnv(env_cfg or EnvConfig(), device=device)
         if overlap is True or overlap is False:
             overlap = "full" if overlap else "none"
@@ -206,7 +222,8 @@ class Trainer:
         env, agent = self.env, self.agent
         if self.fused:
             eps, greedy, out = agent.act_inputs(self.obs)
-            res = env.step_fused(agent.np_state, eps, greedy, out, agent.ring, self.obs)
+            # (store_ring: agent.ring, or the staging ring of n-step returns)
+            res = env.step_fused(agent.np_state, eps, greedy, out, agent.store_ring, self.obs)
             agent.remembered()
             return res
         actions = agent.act(self.obs)                          # train.py:211-222

@@ -69,7 +69,10 @@ const char *dmdqn_last_error(void);
  * dmdqn_agent_hparams with dmdqn_learn_hp, dmdqn_learn_grad_hp,
  * dmdqn_adam_agents_hp and dmdqn_target_soft_update_hp are new -- per-agent
  * learning rate, gamma and tau (a hyperparameter sweep across the env replicas
- * of one run); dmdqn_learn_args and the entry points without _hp are unchanged. */
+ * of one run); dmdqn_learn_args and the entry points without _hp are unchanged.
+ * dmdqn_replay_nstep_commit with dmdqn_nstep_args is new -- n-step returns
+ * built at the replay store: the learn entry points and their structs are
+ * unchanged and receive gamma^n for gamma. */
 int dmdqn_version(void);
 
 /* The digest of the sources this library was built from (16 hex chars:
@@ -234,6 +237,50 @@ int dmdqn_replay_store_f32(int NA, int cap, int slot, const float *obs_s, const 
 int dmdqn_replay_gather_f32(const float *rows_s, const float *rows_n, const int32_t *idx,
                             int NA, int cap, int start, int batch, float *xs, float *xn,
                             void *stream);
+
+/* n-step returns (multi-step TD targets; docs/improvements.md item 7 -- the
+ * reference's ReplayBuffer.add, dqn_agent.py:31-57, stores one-step transitions
+ * and its target, :347, is y = r + gamma (1 - d) Q_t(s', argmax Q(s'))).  The
+ * caller keeps the last n raw transitions of every agent in a staging ring: a
+ * replay ring of n slots in the layout above (st_* = the ring arrays of
+ * dmdqn_replay_store / _store_f32 or dmdqn_env_step with cap = n).  With the
+ * window = staging slots head, head+1, ... (mod n), oldest first, T_0..T_(n-1):
+ *     m = the smallest j in 1..n with d_(j-1) != 0, or n if there is none
+ *     R = r_0;  w = 1.0
+ *     for j in 1..m-1:  w = w * g;  R = R + w * r_j
+ * (g the f64 gamma; every * and + one rounded f64 operation, in this order, no
+ * fma) the call writes the transition (s_0, a_0, R, s'_(m-1), d_(m-1)) into
+ * slot `slot` of the replay ring (capacity `cap`), every byte as the store
+ * entry points write it: the s row verbatim, the s' row of entry m-1 (int8
+ * rows: with a_0 | d << 8 in the word at DMDQN_ROW_A and the bits of R in the
+ * two words at DMDQN_ROW_R), and the same a, R, d in ring_a / ring_r / ring_d.
+ * A window that reaches an episode end is cut there (d = 1 masks the learn's
+ * bootstrap), so the learn of these transitions takes gamma^n for gamma.  With
+ * n = 1 the ring receives what the store entry point itself writes.
+ * row_format: DMDQN_ROWS_I8 (rows of DMDQN_ROW_BYTES) or DMDQN_ROWS_F32 (rows
+ * of DMDQN_ROW_FLOATS f32), the same for the staging ring and the replay ring.
+ * gamma_a: f64 [NA] per-agent gamma (a gamma sweep), or NULL: the scalar gamma.
+ * Refused on the host before any launch (DMDQN_EINVAL): n outside
+ * 1..DMDQN_NSTEP_MAX, head outside [0, n), slot outside [0, cap), NA <= 0, an
+ * unknown row_format, a null array, and -- without gamma_a -- a gamma that is
+ * not finite in [0, 1]. */
+#define DMDQN_NSTEP_MAX 32
+typedef struct dmdqn_nstep_args {
+    int32_t NA, n, head;          /* agents; window length; slot of the oldest  */
+    int32_t cap, slot;            /* replay ring: physical slots, slot to write */
+    int32_t row_format;           /* DMDQN_ROWS_I8 | DMDQN_ROWS_F32              */
+    const void *st_s, *st_n;      /* staging rows [NA][n][row]                   */
+    const uint8_t *st_a;          /* [NA][n]                                     */
+    const double *st_r;           /* [NA][n]                                     */
+    const uint8_t *st_d;          /* [NA][n]                                     */
+    void *ring_s, *ring_n;        /* replay rows [NA][cap][row]                  */
+    uint8_t *ring_a;              /* [NA][cap]                                   */
+    double *ring_r;               /* [NA][cap]                                   */
+    uint8_t *ring_d;              /* [NA][cap]                                   */
+    double gamma;                 /* used when gamma_a is NULL                   */
+    const double *gamma_a;        /* [NA] or NULL                                */
+} dmdqn_nstep_args;
+int dmdqn_replay_nstep_commit(const dmdqn_nstep_args *args, void *stream);
 
 /* Replaces random.sample(self.buffer, k) (dqn_agent.py:63): per env, agents
  * j = 0..A-1 in order draw k deque positions (0 = oldest) from a deque of

@@ -62,10 +62,17 @@ class ReplayBuffer:
     def add(self, experience: tuple):
         state, action, reward, next_state, done = experience
         s, n = _as_obs(state, self.device), _as_obs(next_state, self.device)
-        self.ring.store(s.reshape(1, 89), n.reshape(1, 89),
-                        torch.tensor([int(action)], dtype=torch.int32, device=self.device),
-                        torch.tensor([float(reward)], dtype=torch.float64, device=self.device),
-                        torch.tensor([int(bool(done))], dtype=torch.uint8, device=self.device))
+        # a DQNAgent with config key "n_step" > 1: the raw transition goes to
+        # its staging ring, and from the n_step-th add on each add commits one
+        # n-step transition into self.ring (BatchedDQN.commit_nstep)
+        core = getattr(self, "_core", None)
+        ring = self.ring if core is None else core.store_ring
+        ring.store(s.reshape(1, 89), n.reshape(1, 89),
+                   torch.tensor([int(action)], dtype=torch.int32, device=self.device),
+                   torch.tensor([float(reward)], dtype=torch.float64, device=self.device),
+                   torch.tensor([int(bool(done))], dtype=torch.uint8, device=self.device))
+        if core is not None:
+            core.commit_nstep()
 
     def sample(self, batch_size: int):
         """(states, actions, z-scored rewards, next_states, dones) as device tensors,
@@ -124,6 +131,10 @@ class DQNAgent:
         self._core = BatchedDQN(1, 1, cfg, device=self.device, streams=_streams(self.device))
         self.replay_buffer = ReplayBuffer.__new__(ReplayBuffer)
         self.replay_buffer.device, self.replay_buffer.ring = self.device, self._core.ring
+        # additive config key "n_step" (AgentConfig.n_step): n-step returns;
+        # the buffer then holds n-step transitions, n_step - 1 adds behind
+        self.n_step = self._core.n_step
+        self.replay_buffer._core = self._core
         self.global_step_count = 0
         self.learn_step_counter = 0
         # the per-learn scalars the reference writes with tf.summary to

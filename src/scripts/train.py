@@ -15,6 +15,7 @@ stage for all agents (dmdqn_amd.trainer.Trainer) -- the throughput path.
   python -m src.scripts.train --batched --envs 1024 --grid 4x4 --episodes 1
   python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 \
       --sweep learning_rate=1e-4,5e-4,1e-3          # 3 variants in one run, ranked
+  python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 --n_step 3
 """
 import argparse
 import json
@@ -95,12 +96,15 @@ def create_agents(tl_junctions, config=AGENT_CONFIG):
     return {j: DQNAgent(state_size=89, action_size=4, agent_id=j, config=config) for j in tl_junctions}
 
 
-def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG):
+def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG, n_step=1):
     """AGENT_CONFIG with the target-network rule of --tau /
     --target_update_frequency: soft updates (dqn_agent.py:372-373, 389-399) of
     rate tau after every learn, hard syncs every target_update_frequency learns
-    (0 = never; None = the config's)."""
+    (0 = never; None = the config's); and --n_step: n-step returns built at the
+    replay store (AgentConfig.n_step; 1 = the reference's one-step transitions)."""
     config = dict(config)
+    if n_step != 1:
+        config["n_step"] = n_step
     if tau:
         config["tau"] = float(tau)
     if target_update_frequency is not None:
@@ -131,10 +135,11 @@ def parse_sweep(items):
 
 
 def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenario=None,
-                 save_dir=None, tau=0.0, target_update_frequency=None):
+                 save_dir=None, tau=0.0, target_update_frequency=None, n_step=1):
     dqn_agent.seed(seed)
     env, tl_junctions = initialize_environment(rows, cols, seed, scenario=scenario)
-    agents = create_agents(tl_junctions, target_config(tau, target_update_frequency))
+    agents = create_agents(tl_junctions,
+                           target_config(tau, target_update_frequency, n_step=n_step))
     assert len(agents) == env.R * env.C
     smooth_total = SmoothedValue(alpha=0.3)
     out = open(metrics, "w") if metrics else None
@@ -169,7 +174,7 @@ def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenar
 
 def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, scenario=None,
                   shared=False, save_dir=None, resume=None, log_every=20, loss="mse",
-                  actuated=False, tau=0.0, target_update_frequency=None, sweep=None):
+                  actuated=False, tau=0.0, target_update_frequency=None, sweep=None, n_step=1):
     """E env replicas of the loop on the GPU.  The optional JSONL carries the
     reference's learn scalars (dqn_agent.py:361-370: loss, epsilon,
     q_values_mean / _std, action_distribution) and its per-step rewards with
@@ -182,7 +187,7 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     of the best variant's first replica (the checkpoint holds them all)."""
     from dmdqn_amd.agent import AgentConfig
     from dmdqn_amd.trainer import Trainer
-    cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency))
+    cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency, n_step=n_step))
     cfg.precision, cfg.seed, cfg.shared_params, cfg.loss = precision, seed, shared, loss
     cfg.sweep = sweep
     tr = Trainer(EnvConfig(rows=rows, cols=cols, num_envs=envs, seed=seed, scenario=scenario,
@@ -320,9 +325,16 @@ def main():
                     help="batched only, repeatable: a hyperparameter sweep across the env "
                          "replicas (KEY: learning_rate, gamma or tau); the variants are the grid "
                          "of all --sweep lists, replica g runs variant g mod G")
+    ap.add_argument("--n_step", type=int, default=1,
+                    help="n-step returns: every stored transition carries the discounted sum of "
+                         "up to N rewards and the learn bootstraps with gamma^N (1..32; 1 = the "
+                         "reference's one-step transitions); the last N-1 raw transitions of a "
+                         "run are never stored")
     args = ap.parse_args()
     try:
         sweep = parse_sweep(args.sweep)
+        from dmdqn_amd.agent import check_n_step
+        check_n_step(args.n_step, AGENT_CONFIG["replay_buffer_size"])
     except ValueError as e:
         ap.error(str(e))
     if sweep and not args.batched:
@@ -337,10 +349,10 @@ def main():
     if args.batched:
         train_batched(args.episodes, rows, cols, args.envs, args.precision, args.seed, args.metrics,
                       scenario, args.shared, args.save_dir, args.resume, args.log_every, args.loss,
-                      args.actuated, args.tau, args.target_update_frequency, sweep)
+                      args.actuated, args.tau, args.target_update_frequency, sweep, args.n_step)
     else:
         train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir,
-                     args.tau, args.target_update_frequency)
+                     args.tau, args.target_update_frequency, args.n_step)
 
 
 if __name__ == "__main__":
