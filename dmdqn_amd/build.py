@@ -70,7 +70,7 @@ EXTRA = os.environ.get("DMDQN_EXTRA_FLAGS", "").split()
 # stale): the learn kernels, and the env step (sim + fused observe / store).
 KERNEL_SOURCES = {
     "learn": ["learn.hip", "learn_f16.hip", "learn_bf16.hip", "learn_h16.hpp", "learn_shared.hip",
-              "qnet_layout.hpp", "common.hpp"],
+              "learn_rules.hpp", "learn_img.hpp", "qnet_layout.hpp", "common.hpp"],
     "sim": ["sim.hip", "sim.hpp", "observe.hpp", "common.hpp"],
 }
 

@@ -18,13 +18,14 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "learn_rules.hpp"
 #include "qnet_layout.hpp"
 
 namespace dmdqn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int B_ = 128;     // batch (dqn_agent.py: batch_size 128)
+constexpr int B_ = LEARN_B; // batch (dqn_agent.py: batch_size 128)
 constexpr int D_ = 89;      // observation dim
 constexpr int DP = 96;      // padded feature stride of the X image in LDS
 constexpr int NACT = 4;
@@ -42,18 +43,7 @@ struct Lay : QL<H> {
     static constexpr int H2_OFF = H1_OFF + B_ * H * 4;
     static constexpr int SC_OFF = H2_OFF + B_ * H * 4;
     static constexpr int LDS = SC_OFF + 6400;
-};
-
-struct Scratch {
-    float *z3;    // [128][4]  target Q(S') then online Q(S)
-    float *rn;    // [128] z-scored reward
-    float *y;     // [128] TD target
-    int *act;     // [128]
-    float *dq;    // [128] dL/dq
-    int *slot;    // [128]
-    float *dn;    // [128] done
-    double *r64;  // [128]
-    double *red;  // [16]
+    static_assert(SCRATCH_BYTES <= 6400, "per-row scratch");
 };
 
 // Y[b][n] = act(X[b][:] . W[:][n] + bias[n]) for the wave's 16-column tile.
@@ -131,15 +121,11 @@ struct AdamK {
     bool soft;
 };
 
-// Keras-3 Adam (keras/src/optimizers/adam.py update_step) for one element.
+// Keras-3 Adam (keras_adam_el) on element i, then the target write-out.
 __device__ __forceinline__ void adam_el(float *w, float *m, float *v, float *tgt, size_t i,
                                         float g, const AdamK &K, bool sync) {
-    // each op rounded as TF's separate kernels (mul_rn: this file is built with
-    // -ffp-contract=fast, which ignores the contract pragma)
     float mi = m[i], vi = v[i], wi = w[i];
-    mi = mi + mul_rn(g - mi, K.c1);
-    vi = vi + mul_rn(mul_rn(g, g) - vi, K.c2);
-    wi = wi - (mi * K.alpha) / (sqrtf(vi) + K.eps);
+    keras_adam_el(wi, mi, vi, g, K.alpha, K.c1, K.c2, K.eps);
     m[i] = mi;
     v[i] = vi;
     w[i] = wi;
@@ -165,10 +151,7 @@ __global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a, HpArg<HP>
     using TX = typename std::conditional<XF, float, _Float16>::type;
     float *H1 = (float *)(smem + L::H1_OFF);
     float *H2 = (float *)(smem + L::H2_OFF);
-    char *sc = smem + L::SC_OFF;
-    Scratch S{(float *)sc,           (float *)(sc + 2048), (float *)(sc + 2560),
-              (int *)(sc + 3072),    (float *)(sc + 3584), (int *)(sc + 4096),
-              (float *)(sc + 4608),  (double *)(sc + 5120), (double *)(sc + 6144)};
+    const Scratch S = scratch_at(smem + L::SC_OFF);
     const int agent = blockIdx.x;
     if constexpr (HP) hp_apply(a, hp, agent);
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
@@ -197,50 +180,9 @@ __global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a, HpArg<HP>
         S.r64[tid] = a.ring_r[r];
         S.dn[tid] = a.ring_d[r] ? 1.0f : 0.0f;
     }
-    __syncthreads();
-    // ---- reward z-score (dqn_agent.py:66-69): numpy pairwise sum of 128 f64
-    // (8 interleaved accumulators, tree combine), population std, +1e-8.
-    if (w == 0) {
-        double acc = 0.0;
-        if (l < 8) {
-            acc = S.r64[l];
-            for (int i = 1; i < 16; i++) acc = __dadd_rn(acc, S.r64[8 * i + l]);
-            S.red[l] = acc;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double *r = S.red;
-        double sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                               __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-        sum = __dadd_rn(0.0, sum);
-        S.red[8] = __ddiv_rn(sum, 128.0);
-    }
-    __syncthreads();
-    if (w == 0 && l < 8) {
-        const double mean = S.red[8];
-        double acc = 0.0;
-        for (int i = 0; i < 16; i++) {
-            double d = __dsub_rn(S.r64[8 * i + l], mean);
-            double sq = __dmul_rn(d, d);
-            acc = i == 0 ? sq : __dadd_rn(acc, sq);
-        }
-        S.red[l] = acc;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double *r = S.red;
-        double sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                               __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-        sum = __dadd_rn(0.0, sum);
-        S.red[9] = __dadd_rn(__dsqrt_rn(__ddiv_rn(sum, 128.0)), 1e-8);
-    }
-    __syncthreads();
-    if (tid < B_) {
-        double z = __ddiv_rn(__dsub_rn(S.r64[tid], S.red[8]), S.red[9]);
-        S.rn[tid] = (float)z;
-        if (a.rn_out) a.rn_out[(size_t)agent * B_ + tid] = (float)z;
-    }
+    // ---- reward z-score (its first barrier completes the metadata)
+    zscore(S);
+    if (a.rn_out && tid < B_) a.rn_out[(size_t)agent * B_ + tid] = S.rn[tid];
 
     // ---- P1: gather S' rows
     auto gather = [&](const int8_t *ring) {
@@ -267,17 +209,7 @@ __global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a, HpArg<HP>
     forward<H, TX, HP>(a.target + agent * P, X, H1, H2, S.z3);
     // online forward on S': layer 3 reads H2 only, so its Q goes to the H1 region
     forward<H, TX, HP>(Wp, X, H1, H2, H1);
-    if (tid < B_) {
-        // y = r + (gamma (1 - d)) q_t, each op rounded as TF's (mul_rn: no fma)
-        const float *qo = H1 + tid * NACT;
-        int best = 0;
-        for (int k = 1; k < NACT; k++)
-            if (qo[k] > qo[best]) best = k;  // tf.argmax: first max
-        float tq = S.z3[tid * NACT + best];
-        float gd = a.gamma * (1.0f - S.dn[tid]);
-        S.y[tid] = S.rn[tid] + mul_rn(gd, tq);
-    }
-    __syncthreads();
+    ddqn_target(a, H1, S);
     // ---- P4/P5: gather S, online forward keeping H1, H2; q, loss, dq
     if constexpr (XF) {
         X = a.xs + (size_t)agent * B_ * DP;
@@ -287,20 +219,7 @@ __global__ void __launch_bounds__(512) k_learn_f32(dmdqn_learn_args a, HpArg<HP>
     }
     forward<H, TX, HP>(Wp, X, H1, H2, S.z3);
     if (a.qstats) learn_qstats(a.qstats, agent, S.z3, S.act);
-    float lsum = 0.0f;
-    if (tid < B_) {
-        float q = S.z3[tid * NACT + S.act[tid]];
-        float dq;
-        loss_term(a.loss_kind, q - S.y[tid], 1.0f / (float)B_, lsum, dq);
-        S.dq[tid] = dq;
-    }
-    // loss: wave reductions then one lane
-    if (w < 2) {
-        for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off);
-        if (l == 0) S.red[10 + w] = (double)lsum;
-    }
-    __syncthreads();
-    if (tid == 0 && a.loss) a.loss[agent] = (float)(S.red[10] + S.red[11]) / (float)B_;
+    loss_rows(a, agent, S, [&](int row, float dq) { S.dq[row] = dq; });
 
     // ---- backward
     // dW3[k][a] = sum_b H2[b][k] dq3[b][a] ; db3[a]  (VALU, one thread per element)
@@ -518,13 +437,10 @@ __global__ void __launch_bounds__(256) k_target_soft(const float *params, float 
         omt = omt_a[q / P4];
     }
     const float4 w = reinterpret_cast<const float4 *>(params)[q];
-    float4 t = reinterpret_cast<const float4 *>(target)[q];
-    t.x = soft_el(w.x, t.x, tau, omt);
-    t.y = soft_el(w.y, t.y, tau, omt);
-    t.z = soft_el(w.z, t.z, tau, omt);
-    t.w = soft_el(w.w, t.w, tau, omt);
+    const float4 t = soft_el4(w, reinterpret_cast<const float4 *>(target)[q], tau, omt);
     reinterpret_cast<float4 *>(target)[q] = t;
     if (target_h) {
+        // (shadow4's store, learn_rules.hpp, with this kernel's own index order)
         const long net = q / P4, k = q - net * P4;
         typedef T16 t16x4 __attribute__((ext_vector_type(4)));
         t16x4 hv;

@@ -44,9 +44,8 @@ __global__ void __launch_bounds__(512) k_reduce_slabs(const float *slab, int nw,
 
 }  // namespace f16k
 
-// One Keras-3 Adam update (A-11) of parameter i with gradient gr, each op
-// rounded as TF's separate kernels (mul_rn: this file is built with
-// -ffp-contract=fast, which ignores the contract pragma); on a target sync
+// One Keras-3 Adam update (A-11; keras_adam_el, learn_rules.hpp) of parameter i
+// with gradient gscale * gr (a rounded product of its own); on a target sync
 // also the target copy and its f16 shadow.  Shared by k_adam and
 // k_reduce_adam, so both compute the same bits.
 struct AdamK {
@@ -56,10 +55,7 @@ struct AdamK {
     int sync;
 };
 __device__ __forceinline__ void keras_adam1(const AdamK &k, int i, float gr, float w, float m, float v) {
-    const float g = mul_rn(gr, k.gscale);
-    m = m + mul_rn(g - m, k.c1);
-    v = v + mul_rn(mul_rn(g, g) - v, k.c2);
-    w = w - (m * k.alpha) / (sqrtf(v) + k.eps);
+    keras_adam_el(w, m, v, mul_rn(gr, k.gscale), k.alpha, k.c1, k.c2, k.eps);
     k.M[i] = m;
     k.V[i] = v;
     k.W[i] = w;

@@ -40,6 +40,8 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "learn_img.hpp"
+#include "learn_rules.hpp"
 #include "qnet_layout.hpp"
 
 #if DMDQN_H16_BF16
@@ -72,10 +74,8 @@ typedef H16_T h16;  // the MFMA operand type (f16 or bf16)
 typedef h16 half8 __attribute__((ext_vector_type(8)));
 typedef h16 half4v __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short v4s __attribute__((vector_size(8)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
 
-constexpr int B_ = 128, DP = QN_DP, H = 128, NACT = QN_NA;
+constexpr int B_ = LEARN_B, DP = QN_DP, H = 128, NACT = QN_NA;
 using L = QL<H>;
 
 // LDS byte offsets
@@ -84,6 +84,7 @@ constexpr int R2_OFF = R1_OFF + B_ * H * 2;
 constexpr int DQ_OFF = R2_OFF + B_ * H * 2;
 constexpr int SC_OFF = DQ_OFF + B_ * 16 * 2;
 constexpr int W3_OFF = SC_OFF + 6272;          // f16 W3T images [2][4][128]: online, target
+static_assert(SCRATCH_BYTES <= 6272, "per-row scratch");
 constexpr int B3_OFF = W3_OFF + 2 * NACT * H * 2; // f32 b3 [2][4]
 constexpr int LDS_BYTES = B3_OFF + 2 * NACT * 4;
 static_assert(LDS_BYTES <= 81920, "two workgroups per CU");
@@ -109,46 +110,13 @@ __device__ __forceinline__ half8 frag_row(const h16 *img, int ld, int r0, int k0
     return *reinterpret_cast<const half8 *>(img + (r0 + (l & 15)) * ld + k0 + 8 * (l >> 4));
 }
 
-// img[r0 + 8(l>>4) + e][c0 + (l&15)], e = 0..7: two ds_read_b64_tr_b16.
-// Lane 4q+p of each 16-lane group addresses row q, columns 4p..4p+3 of a
-// 4-row block; lane i receives column i of the block (row q -> element q).
+// img[r0 + 8(l>>4) + e][c0 + (l&15)], e = 0..7 (frag_tr2, learn_img.hpp).
 __device__ __forceinline__ half8 frag_tr(const h16 *img, int ld, int r0, int c0) {
     const int l = threadIdx.x & 63, i = l & 15, g = l >> 4;
-    const h16 *p0 = img + (r0 + 8 * g + (i >> 2)) * ld + c0 + 4 * (i & 3);
-    v4s t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)p0);
-    v4s t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(p0 + 4 * ld));
-    half8 r;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        r[e] = __builtin_bit_cast(h16, (short)t0[e]);
-        r[e + 4] = __builtin_bit_cast(h16, (short)t1[e]);
-    }
-    return r;
+    return frag_tr2(img + (r0 + 8 * g + (i >> 2)) * ld + c0 + 4 * (i & 3), 4 * ld);
 }
 
-// The activation images -- [128][128] H1, H2, dZ2, dZ1, the W2^T image and
-// the [128][96] X -- are stored in 8-row x 32-column blocks of 512 B (a band
-// of 8 rows is LD/32 blocks, a multiple of 256 B),
-// row r's 16-byte chunks within a block XOR-permuted by bit 1 and bit 3 of r
-// (a search over the linear permutations of row bits 0, 1, 3):
-//   * row-fragment reads (ds_read_b128 of rows r0..r0+15, chunk 4s+lg): each
-//     16-lane bank group {0-3,12-15 | 20-27} covers all 16 bank slots;
-//   * transposed reads (ds_read_b64_tr_b16 of rows r0+8g+q, chunks 2c..2c+1):
-//     each 32-lane half covers all 32 eight-byte slots;
-// so both are conflict-free (the plain 256-B rows were 8-way on both), the
-// 8-byte MFMA-output stores are 2-way (the least any permutation of whole
-// 16-byte chunks allows for 16 rows at one column), and
-// every address is a lane constant plus an immediate.  (The 2-way conflicts
-// of the 192-B X rows go too.)
-template <int LD = H>
-__device__ __forceinline__ int hoff(int r, int c) {
-    static_assert(LD % 32 == 0, "whole blocks per band");
-    const int ch = c >> 3;
-    return 8 * LD * (r >> 3) + 256 * (ch >> 2) + 32 * (r & 7) +
-           8 * ((ch & 3) ^ (((r >> 1) & 1) | ((r >> 2) & 2))) + (c & 7);
-}
-
-// frag_row on a blocked image (r0 a multiple of 16, k0 of 32).
+// frag_row on a blocked image (hoff, learn_img.hpp; r0 a multiple of 16, k0 of 32).
 template <int LD = H>
 __device__ __forceinline__ half8 frag_row_h(const h16 *img, int r0, int k0, int tid = threadIdx.x) {
     const int l = tid & 63;
@@ -160,16 +128,7 @@ __device__ __forceinline__ half8 frag_row_h(const h16 *img, int r0, int k0, int 
 template <int LD = H>
 __device__ __forceinline__ half8 frag_tr_h(const h16 *img, int r0, int c0) {
     const int l = threadIdx.x & 63, i = l & 15, g = l >> 4;
-    const h16 *p0 = img + hoff<LD>(r0 + 8 * g + (i >> 2), c0 + 4 * (i & 3));
-    v4s t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)p0);
-    v4s t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(p0 + 128));
-    half8 r;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        r[e] = __builtin_bit_cast(h16, (short)t0[e]);
-        r[e + 4] = __builtin_bit_cast(h16, (short)t1[e]);
-    }
-    return r;
+    return frag_tr2(img + hoff<LD>(r0 + 8 * g + (i >> 2), c0 + 4 * (i & 3)), 128);
 }
 
 // A-fragment of a transposed f32 weight matrix WT[N][ld] (tiled, qn_wt)
@@ -257,13 +216,6 @@ __device__ __forceinline__ half8 ones8() {
     for (int e = 0; e < 8; e++) r[e] = (h16)1.0f;
     return r;
 }
-
-struct Scratch {
-    float *z3;  // [128][4]
-    float *rn, *y, *dq, *dn;
-    int *act, *slot;
-    double *r64, *red;
-};
 
 // Per-wave register copy of one network's weights: the A-fragments of the
 // wave's 16 neurons for layers 1 and 2, the (4-row) output layer, and the
@@ -432,18 +384,6 @@ __device__ void forward_x(Frags &f, const OutL o, const h16 *X, h16 *H1b, h16 *H
 // A gradient entry as Adam receives it under the mixed policy: 16-bit.
 __device__ __forceinline__ float gval(const f32x4 &g, int e) { return r16(g[e]); }
 
-// Keras-3 Adam (keras/src/optimizers/adam.py update_step) on one parameter,
-// every op rounded on its own as TF's separate elementwise kernels do: no fma
-// contraction (mul_rn: this file is built with -ffp-contract=fast for the
-// MFMA epilogues, which ignores the contract pragma), correctly rounded sqrt
-// and divide (HIP's default).
-__device__ __forceinline__ void adam_el(float &w, float &m, float &v, float g, float alpha,
-                                        float c1, float c2, float eps) {
-    m = m + mul_rn(g - m, c1);
-    v = v + mul_rn(mul_rn(g, g) - v, c2);
-    w = w - (m * alpha) / (sqrtf(v) + eps);
-}
-
 // What a learn's Adam epilogue does to the target network (compile-time in the
 // kernels: no run-time branch in the Adam streams): nothing, the hard copy
 // target <- online (dqn_agent.py:376-387), or the soft update target <-
@@ -459,21 +399,12 @@ struct AdamC {
     float tau, omt;  // TGT_SOFT: float32(tau), float32(1 - tau)
 };
 
-// The soft update of a lane's 4 parameters: t (the f32 target loaded with w, m,
-// v) becomes soft_el(w, t), stored to T and, rounded to 16 bits, to TH.
-__device__ __forceinline__ void soft4(float *T, h16 *TH, size_t i, const float4 &w, float4 t,
-                                      const AdamC &k) {
-    t.x = soft_el(w.x, t.x, k.tau, k.omt);
-    t.y = soft_el(w.y, t.y, k.tau, k.omt);
-    t.z = soft_el(w.z, t.z, k.tau, k.omt);
-    t.w = soft_el(w.w, t.w, k.tau, k.omt);
-    *reinterpret_cast<float4 *>(T + i) = t;
-    if (TH) {
-        half4v hv;
-        hv[0] = (h16)t.x; hv[1] = (h16)t.y;
-        hv[2] = (h16)t.z; hv[3] = (h16)t.w;
-        *reinterpret_cast<half4v *>(TH + i) = hv;
-    }
+// The target write-out of a lane's 4 parameters at index i after Adam (w: the
+// new online values; t: the old f32 target, loaded with w, m, v on a soft learn).
+__device__ __forceinline__ void target4(float *T, size_t i, const float4 &w, const float4 &t,
+                                        const AdamC &k) {
+    if (k.tmode == TGT_HARD) target_hard4(T + i, k.TH, i, w);
+    if (k.tmode == TGT_SOFT) target_soft4(T + i, k.TH, i, w, t, k.tau, k.omt);
 }
 
 // Keras-3 Adam on NT groups of 4 consecutive parameters (one 16-byte lane
@@ -506,23 +437,14 @@ __device__ __forceinline__ void adam4n(float *W, float *M, float *V, float *T, c
         float *pw = &w[q].x, *pm = &m[q].x, *pv = &v[q].x;
 #pragma unroll
         for (int e = 0; e < 4; e++)
-            adam_el(pw[e], pm[e], pv[e], gval(g[q], e), k.alpha, k.c1, k.c2, k.eps);
+            keras_adam_el(pw[e], pm[e], pv[e], gval(g[q], e), k.alpha, k.c1, k.c2, k.eps);
     }
 #pragma unroll
     for (int q = 0; q < NT; q++) {
         *reinterpret_cast<float4 *>(W + idx[q]) = w[q];
         *reinterpret_cast<float4 *>(M + idx[q]) = m[q];
         *reinterpret_cast<float4 *>(V + idx[q]) = v[q];
-        if (k.tmode == TGT_HARD) {
-            *reinterpret_cast<float4 *>(T + idx[q]) = w[q];
-            if (k.TH) {
-                half4v hv;
-                hv[0] = (h16)w[q].x; hv[1] = (h16)w[q].y;
-                hv[2] = (h16)w[q].z; hv[3] = (h16)w[q].w;
-                *reinterpret_cast<half4v *>(k.TH + idx[q]) = hv;
-            }
-        }
-        if (k.tmode == TGT_SOFT) soft4(T, k.TH, idx[q], w[q], tg[q], k);
+        target4(T, idx[q], w[q], tg[q], k);
     }
 }
 
@@ -536,29 +458,17 @@ __device__ __forceinline__ void adam4n(float *W, float *M, float *V, float *T, c
 // `grad()` runs after the first batch's loads are issued and produces g[]:
 // the w, m, v loads do not depend on the gradient, so their latency hides
 // behind the gradient MFMAs.
-// Issue the first Adam batch before the gradient MFMAs: for W1 (measured
+// EARLY: issue the first Adam batch before the gradient MFMAs: for W1 (measured
 // 1-2 % faster); not for W2, where the 24 extra live VGPRs next to the dW2
 // accumulators and the W2 fragments spill (10 -> 28) and cost 10 %.
-#ifndef DMDQN_EARLY_W3
-#define DMDQN_EARLY_W3 0
-#endif
-#ifndef DMDQN_GX_EARLY
-#define DMDQN_GX_EARLY 0
-#endif
-#ifndef DMDQN_EARLY_W2
-#define DMDQN_EARLY_W2 0
-#endif
-#ifndef DMDQN_EARLY_W1
-#define DMDQN_EARLY_W1 1
-#endif
-// Soft target update in the pipe: 1 = the old target of batch h is loaded at
+// Soft target update in the pipe: the old target of batch h is loaded at
 // the top of iteration h, ahead of batch h+1's w, m, v (vmcnt is in-order, so
-// its wait does not cover them): one buffer, 4 NT fewer live VGPRs; 0 = it is
-// double-buffered with w, m, v.  Measured (C3 and C2, fp16 and bf16): 1 is
+// its wait does not cover them): one buffer, 4 NT fewer live VGPRs than
+// double-buffering it with w, m, v.  Measured (C3 and C2, fp16 and bf16):
 // 2.7-4 % faster, scratch 84 -> 44-52 B per lane.
-#ifndef DMDQN_SOFT_TG_SINGLE
-#define DMDQN_SOFT_TG_SINGLE 1
-#endif
+// (Retired switches, DESIGN §6: DMDQN_EARLY_W1 / _W2 / _W3, DMDQN_GX_EARLY and
+// DMDQN_SOFT_TG_SINGLE; rebuild a variant for a same-box A/B with
+// tools/build_rev.py 2521462 <name> -D<switch>=<0|1>.)
 // `valid(tile)` says whether the lane's 4 parameters of that tile exist (the
 // W1 block stores only features 0..88; a lane with nothing to update keeps its
 // registers and touches no memory).
@@ -580,6 +490,9 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
                     make_float4(gval(g[t], 0), gval(g[t], 1), gval(g[t], 2), gval(g[t], 3));
         return;
     }
+    // (tg keeps the extent of the retired double-buffered form and uses half 0:
+    // declared as tg[NT] the pipe's phis, and with them the register allocation
+    // of every fused learn kernel, come out in another order)
     float4 w[2][NT], m[2][NT], v[2][NT], tg[2][NT];
     if constexpr (!EARLY) grad();
 #pragma unroll
@@ -590,8 +503,6 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
             w[0][q] = *reinterpret_cast<const float4 *>(W + i);
             m[0][q] = *reinterpret_cast<const float4 *>(M + i);
             v[0][q] = *reinterpret_cast<const float4 *>(V + i);
-            if (!DMDQN_SOFT_TG_SINGLE && k.tmode == TGT_SOFT)
-                tg[0][q] = *reinterpret_cast<const float4 *>(T + i);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -601,8 +512,8 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
     }
 #pragma unroll
     for (int h = 0; h < NB; h++) {
-        const int c = h & 1, n = c ^ 1, ct = DMDQN_SOFT_TG_SINGLE ? 0 : c;
-        if (DMDQN_SOFT_TG_SINGLE && k.tmode == TGT_SOFT) {
+        const int c = h & 1, n = c ^ 1;
+        if (k.tmode == TGT_SOFT) {
 #pragma unroll
             for (int q = 0; q < NT; q++)
                 if (valid(h * NT + q))
@@ -617,8 +528,6 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
                     w[n][q] = *reinterpret_cast<const float4 *>(W + i);
                     m[n][q] = *reinterpret_cast<const float4 *>(M + i);
                     v[n][q] = *reinterpret_cast<const float4 *>(V + i);
-                    if (!DMDQN_SOFT_TG_SINGLE && k.tmode == TGT_SOFT)
-                        tg[n][q] = *reinterpret_cast<const float4 *>(T + i);
                 }
             }
         }
@@ -629,7 +538,7 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
             const GT gq = g[h * NT + q];
 #pragma unroll
             for (int e = 0; e < 4; e++)
-                adam_el(pw[e], pm[e], pv[e], gval(gq, e), k.alpha, k.c1, k.c2, k.eps);
+                keras_adam_el(pw[e], pm[e], pv[e], gval(gq, e), k.alpha, k.c1, k.c2, k.eps);
         }
 #pragma unroll
         for (int q = 0; q < NT; q++) {
@@ -638,16 +547,7 @@ __device__ __forceinline__ void adam_pipe(float *W, float *M, float *V, float *T
             *reinterpret_cast<float4 *>(W + i) = w[c][q];
             *reinterpret_cast<float4 *>(M + i) = m[c][q];
             *reinterpret_cast<float4 *>(V + i) = v[c][q];
-            if (k.tmode == TGT_HARD) {
-                *reinterpret_cast<float4 *>(T + i) = w[c][q];
-                if (k.TH) {
-                    half4v hv;
-                    hv[0] = (h16)w[c][q].x; hv[1] = (h16)w[c][q].y;
-                    hv[2] = (h16)w[c][q].z; hv[3] = (h16)w[c][q].w;
-                    *reinterpret_cast<half4v *>(k.TH + i) = hv;
-                }
-            }
-            if (k.tmode == TGT_SOFT) soft4(T, k.TH, i, w[c][q], tg[ct][q], k);
+            target4(T, i, w[c][q], tg[0][q], k);
         }
     }
 }
@@ -665,7 +565,7 @@ __device__ __forceinline__ void adam1(float *W, float *M, float *V, float *T, si
     }
     float m = M[i], v = V[i], w = W[i], tg = 0.0f;
     if (k.tmode == TGT_SOFT) tg = T[i];
-    adam_el(w, m, v, r16(g), k.alpha, k.c1, k.c2, k.eps);  // the 16-bit gradient
+    keras_adam_el(w, m, v, r16(g), k.alpha, k.c1, k.c2, k.eps);  // the 16-bit gradient
     M[i] = m;
     V[i] = v;
     W[i] = w;
@@ -681,9 +581,8 @@ __device__ __forceinline__ void adam1(float *W, float *M, float *V, float *T, si
 }
 
 // ----------------------------------------------------------------------------
-// Per-agent pieces shared by the independent kernel (k_learn_f16) and the
-// shared-parameter kernel (k_learn_shared_f16).  All are called by every
-// thread of the 512-thread workgroup.
+// Per-agent pieces of the learn kernel.  All are called by every thread of the
+// 512-thread workgroup.
 
 template <bool XF> struct RowsT { uint2 v[3]; };        // int8 rows: 3 x 8 features per thread
 template <> struct RowsT<true> { float4 v[6]; };        // float rows: the same 24 features
@@ -810,46 +709,6 @@ __device__ __forceinline__ void meta_commit(const Meta &m, const Scratch &S) {
     }
 }
 
-// The reward z-score of ReplayBuffer.sample (dqn_agent.py:64-69) over S.r64:
-// f64 mean and population std over the 128 rewards in numpy's pairwise order
-// (8 partial sums of 16), + 1e-8.  Starts with a barrier (S.r64 complete).
-__device__ __forceinline__ void zscore(const Scratch &S) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    if (tid < 8) {
-        double acc = S.r64[tid];
-        for (int i = 1; i < 16; i++) acc = __dadd_rn(acc, S.r64[8 * i + tid]);
-        S.red[tid] = acc;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double *r = S.red;
-        double sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                               __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-        S.red[8] = __ddiv_rn(__dadd_rn(0.0, sum), 128.0);
-    }
-    __syncthreads();
-    if (tid < 8) {
-        const double mean = S.red[8];
-        double acc = 0.0;
-        for (int i = 0; i < 16; i++) {
-            double d = __dsub_rn(S.r64[8 * i + tid], mean);
-            double sq = __dmul_rn(d, d);
-            acc = i == 0 ? sq : __dadd_rn(acc, sq);
-        }
-        S.red[tid] = acc;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double *r = S.red;
-        double sum = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                               __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-        S.red[9] = __dadd_rn(__dsqrt_rn(__ddiv_rn(__dadd_rn(0.0, sum), 128.0)), 1e-8);
-    }
-    __syncthreads();
-    if (tid < B_) S.rn[tid] = (float)__ddiv_rn(__dsub_rn(S.r64[tid], S.red[8]), S.red[9]);
-}
-
 // Slots, then the s' rows -> X(S') in R2 plus the metadata, then the z-score.
 // X(S') is visible to every thread on return (zscore's barriers).  XF: float
 // rows, the metadata from the per-slot arrays.  issued() runs once the row
@@ -880,30 +739,11 @@ __device__ __forceinline__ void batch_head(const dmdqn_learn_args &a, int agent,
     if (a.rn_out && threadIdx.x < B_) a.rn_out[(size_t)agent * B_ + threadIdx.x] = S.rn[threadIdx.x];
 }
 
-// Double-DQN target y = r^ + gamma (1 - d) Q_target(S')[argmax Q_online(S')]
-// (dqn_agent.py:342-347; first max on ties).  qo: online Q(S') [128][4];
-// S.z3: target Q(S').  Ends with a barrier.
-__device__ __forceinline__ void ddqn_target(const dmdqn_learn_args &a, const float *qo,
-                                            const Scratch &S) {
-    const int tid = threadIdx.x;
-    if (tid < B_) {
-        // y = r + (gamma (1 - d)) q_t, each op rounded as TF's (mul_rn: no fma)
-        const float4 q = *reinterpret_cast<const float4 *>(qo + tid * NACT);
-        int best = 0;
-        float bq = q.x;
-        if (q.y > bq) { best = 1; bq = q.y; }
-        if (q.z > bq) { best = 2; bq = q.z; }
-        if (q.w > bq) { best = 3; }
-        float tq = S.z3[tid * NACT + best];
-        float gd = a.gamma * (1.0f - S.dn[tid]);
-        S.y[tid] = S.rn[tid] + mul_rn(gd, tq);
-    }
-    __syncthreads();
-}
-
 // MSE (dqn_agent.py:350-352) or Huber loss (loss_term) of Q_online(S) in S.z3 at
 // the taken actions, written to a.loss[agent]; dL/dQ (f16) into DQ [128][16] and
-// S.dq.  Ends with a barrier.
+// S.dq.  Ends with a barrier.  Must match the bits of loss_rows
+// (learn_rules.hpp): its own form is kept for the QSTATS kernels' generated code
+// (through loss_rows the metrics' early exit and the reduction merge differently).
 template <bool QSTATS>
 __device__ __forceinline__ void loss_dq(const dmdqn_learn_args &a, int agent, h16 *DQ,
                                         const Scratch &S) {
@@ -985,24 +825,6 @@ __device__ __forceinline__ void bwd_dh1_from_image(const h16 *R1, const h16 *R2,
     __syncthreads();
 }
 
-__device__ __forceinline__ void bwd_dh1(h16 *R1, const h16 *R2, const Frags &fr,
-                                        f32x4 d1[8]) {
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, lr = l & 15, lg = l >> 4;
-#pragma unroll
-    for (int s2 = 0; s2 < 4; s2++)
-        *reinterpret_cast<half8 *>(R1 + hoff(16 * w + lr, 32 * s2 + 8 * lg)) = fr.w2[s2];
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 8; t++) d1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s2 = 0; s2 < 4; s2++) {
-        const half8 av = frag_tr_h(R1, 32 * s2, 16 * w);
-#pragma unroll
-        for (int t = 0; t < 8; t++) d1[t] = mfma(av, frag_row_h(R2, 16 * t, 32 * s2), d1[t]);
-    }
-    __syncthreads();
-}
-
 // dZ1 = dH1 masked by ReLU(H1) -> R1 (lane: neurons j..j+3 of row b).
 __device__ __forceinline__ void bwd_dz1(h16 *R1, const uint32_t *mask, const f32x4 d1[8]) {
     // lane ids from fresh_tid: the addresses are recomputed here instead of
@@ -1024,10 +846,7 @@ __device__ __forceinline__ void bwd_dz1(h16 *R1, const uint32_t *mask, const f32
     __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];                              \
     h16 *R1 = (h16 *)(smem + R1_OFF), *R2 = (h16 *)(smem + R2_OFF);                            \
     h16 *DQ = (h16 *)(smem + DQ_OFF);                                                          \
-    char *sc = smem + SC_OFF;                                                                  \
-    Scratch S{(float *)sc,          (float *)(sc + 2048), (float *)(sc + 2560),                \
-              (float *)(sc + 3072), (float *)(sc + 3584), (int *)(sc + 4096),                  \
-              (int *)(sc + 4608),   (double *)(sc + 5120), (double *)(sc + 6144)};             \
+    const Scratch S = scratch_at(smem + SC_OFF);                                               \
     h16 *W3L = (h16 *)(smem + W3_OFF);                                                         \
     float *B3L = (float *)(smem + B3_OFF);                                                     \
     const OutL on{W3L, B3L}, tg{W3L + NACT * H, B3L + NACT};                                   \
@@ -1125,49 +944,6 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
     h16 *const P1 = R2, *const P2 = R1;
     STAMP(7);
     const half8 ones = ones8();
-#if DMDQN_EARLY_W3
-    static_assert(!GOUT && TM != TGT_SOFT, "the early-W3 variant has no split or soft form");
-    // ---- dW3[k][a] = H2^T . DQ (wave w: k-tile w) ; db3 (wave 0).  W3's
-    // Adam loads (lanes lr < 4: rows k = 16w + 4lg + e, column a -> W3T[a][k..k+3])
-    // are issued before the loss, so their latency hides behind it.
-    {
-        const size_t i3 = L::oW3T + (size_t)(lr & 3) * H + 16 * w + 4 * lg;
-        float4 w3 = {}, m3 = {}, v3 = {};
-        if (lr < NACT) {
-            w3 = *reinterpret_cast<const float4 *>(Wp + i3);
-            m3 = *reinterpret_cast<const float4 *>(Mp + i3);
-            v3 = *reinterpret_cast<const float4 *>(Vp + i3);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        loss_dq<QSTATS>(a, agent, DQ, S);
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, gb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int b0 = 0; b0 < B_; b0 += 32) {
-            half8 dqf = frag_tr(DQ, 16, b0, 0);
-            acc = mfma(frag_tr_h(P2, b0, 16 * w), dqf, acc);
-            gb = mfma(ones, dqf, gb);  // every wave (no MFMA under divergent control)
-        }
-        if (lr < NACT) {
-            float *pw = &w3.x, *pm = &m3.x, *pv = &v3.x;
-#pragma unroll
-            for (int e = 0; e < 4; e++)
-                adam_el(pw[e], pm[e], pv[e], r16(acc[e]), AK.alpha, AK.c1, AK.c2, AK.eps);
-            *reinterpret_cast<float4 *>(Wp + i3) = w3;
-            *reinterpret_cast<float4 *>(Mp + i3) = m3;
-            *reinterpret_cast<float4 *>(Vp + i3) = v3;
-            if (TM == TGT_HARD) {
-                *reinterpret_cast<float4 *>(Tp + i3) = w3;
-                if (TH) {
-                    half4v hv;
-                    hv[0] = (h16)w3.x; hv[1] = (h16)w3.y;
-                    hv[2] = (h16)w3.z; hv[3] = (h16)w3.w;
-                    *reinterpret_cast<half4v *>(TH + i3) = hv;
-                }
-            }
-            if (w == 0 && lg == 0) adam1(Wp, Mp, Vp, Tp, L::ob3 + lr, gb[0], AK);
-        }
-    }
-#else
     loss_dq<QSTATS>(a, agent, DQ, S);
     // ---- dW3[k][a] = H2^T . DQ (wave w: k-tile w) ; db3 (wave 0)
     {
@@ -1184,7 +960,6 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
             if (w == 0 && lg == 0) adam1(Wp, Mp, Vp, Tp, L::ob3 + lr, gb[0], AK);
         }
     }
-#endif
     __syncthreads();  // dW3 read H2; dZ2 overwrites it
     STAMP(8);
     bwd_dz2(P2, on, S);
@@ -1194,7 +969,7 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
     {
         f32x4 g2[8], gb = {0.f, 0.f, 0.f, 0.f};
         // rows j = 16w + 4lg + e, column k = 16t + lr  ->  W2T[k][j..j+3]
-        adam_pipe<4, 2, DMDQN_EARLY_W2>(
+        adam_pipe<4, 2, false>(
             Wp, Mp, Vp, Tp,
             [&](int t) { return (size_t)L::oW2T + qn_wt(16 * t + lr, 16 * w + 4 * lg, H); }, g2,
             AK, [&]() {
@@ -1217,22 +992,12 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
     }
     __syncthreads();  // W2^T image complete
     f32x4 d1[8];
-#if DMDQN_GX_EARLY
-    {
-        RowsT<XF> gx;  // X(S) again for dW1: issued before dH1, lands in P2 once dZ2 is consumed
-        gather_x<XF>(a, agent, false, S.slot, gx);
-        __builtin_amdgcn_sched_barrier(0);
-        bwd_dh1_from_image(P1, P2, d1);
-        commit_x<XF>(P2, gx);
-    }
-#else
     bwd_dh1_from_image(P1, P2, d1);
     {
         RowsT<XF> gx;  // X(S) again for dW1 (P2 is free)
         gather_x<XF>(a, agent, false, S.slot, gx);
         commit_x<XF>(P2, gx);
     }
-#endif
     STAMP(10);
     bwd_dz1(P1, mask, d1);
     __syncthreads();
@@ -1245,7 +1010,7 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
         // holds features 80..95: lanes lg < 2 (80..87) update in the pipe, lane
         // lg = 2's first row is feature 88 (the W1T column, below), the rest
         // (89..95) do not exist
-        adam_pipe<2, 3, DMDQN_EARLY_W1>(
+        adam_pipe<2, 3, true>(
             Wp, Mp, Vp, Tp,
             [&](int t) { return (size_t)L::oW1T + qn_w1<H>(16 * w + lr, t < 5 || lg < 2 ? 16 * t + 4 * lg : 0); },
             g1, AK, [&]() {
@@ -1273,7 +1038,7 @@ __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, f
     }
 }
 
-// The split learn's second launch: Keras-3 Adam (adam_el, the fused kernel's
+// The split learn's second launch: Keras-3 Adam (keras_adam_el, the fused kernel's
 // arithmetic) on every agent's P parameters from grad[NA][P]; on a sync (TM =
 // TGT_HARD) or a soft update (TGT_SOFT, soft_el with the old target loaded
 // beside w, m, v) also the f32 target and its 16-bit shadow (agent stride Ph).
@@ -1304,32 +1069,13 @@ __global__ void __launch_bounds__(256) H16_ADAM_KERNEL(float *W, float *M, float
     float *pw = &w.x, *pm = &m.x, *pv = &v.x;
     const float *pg = &g.x;
 #pragma unroll
-    for (int e = 0; e < 4; e++) adam_el(pw[e], pm[e], pv[e], pg[e], alpha, c1, c2, eps);
+    for (int e = 0; e < 4; e++) keras_adam_el(pw[e], pm[e], pv[e], pg[e], alpha, c1, c2, eps);
     *reinterpret_cast<float4 *>(W + i) = w;
     *reinterpret_cast<float4 *>(M + i) = m;
     *reinterpret_cast<float4 *>(V + i) = v;
-    if (TM == TGT_HARD) {
-        *reinterpret_cast<float4 *>(T + i) = w;
-        if (TH) {
-            half4v hv;
-            hv[0] = (h16)w.x; hv[1] = (h16)w.y;
-            hv[2] = (h16)w.z; hv[3] = (h16)w.w;
-            *reinterpret_cast<half4v *>(TH + (size_t)blockIdx.y * Ph + 4 * (size_t)q) = hv;
-        }
-    }
-    if (TM == TGT_SOFT) {
-        t.x = soft_el(w.x, t.x, tau, omt);
-        t.y = soft_el(w.y, t.y, tau, omt);
-        t.z = soft_el(w.z, t.z, tau, omt);
-        t.w = soft_el(w.w, t.w, tau, omt);
-        *reinterpret_cast<float4 *>(T + i) = t;
-        if (TH) {
-            half4v hv;
-            hv[0] = (h16)t.x; hv[1] = (h16)t.y;
-            hv[2] = (h16)t.z; hv[3] = (h16)t.w;
-            *reinterpret_cast<half4v *>(TH + (size_t)blockIdx.y * Ph + 4 * (size_t)q) = hv;
-        }
-    }
+    const size_t ih = (size_t)blockIdx.y * Ph + 4 * (size_t)q;  // the shadow's stride is Ph
+    if (TM == TGT_HARD) target_hard4(T + i, TH, ih, w);
+    if (TM == TGT_SOFT) target_soft4(T + i, TH, ih, w, t, tau, omt);
 }
 
 DMDQN_DBG_READER(dbg_flags)

@@ -26,6 +26,8 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "learn_img.hpp"
+#include "learn_rules.hpp"
 #include "qnet_layout.hpp"
 
 namespace dmdqn {
@@ -35,10 +37,8 @@ typedef _Float16 h16;
 typedef h16 half8 __attribute__((ext_vector_type(8)));
 typedef h16 half4v __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short v4s __attribute__((vector_size(8)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
 
-constexpr int B_ = 128, H = 128, NACT = QN_NA, DP = QN_DP;
+constexpr int B_ = LEARN_B, H = 128, NACT = QN_NA, DP = QN_DP;
 using L = QL<H>;
 
 __device__ __forceinline__ f32x4 mfma(half8 a, half8 b, f32x4 c) {
@@ -60,15 +60,9 @@ __device__ __forceinline__ int kperm(int s, int g, int e) {
 }
 
 // ---------------------------------------------------------------- LDS images
-// The blocked, XOR-permuted activation images of learn_h16.hpp (hoff): 8-row x
+// The blocked, XOR-permuted activation images (hoff, learn_img.hpp): 8-row x
 // 32-column blocks, conflict-free row-fragment and transposed reads.
-template <int LD = H>
-__device__ __forceinline__ int hoff(int r, int c) {
-    const int ch = c >> 3;
-    return 8 * LD * (r >> 3) + 256 * (ch >> 2) + 32 * (r & 7) +
-           8 * ((ch & 3) ^ (((r >> 1) & 1) | ((r >> 2) & 2))) + (c & 7);
-}
-
+//
 // hoff(r, c) = hoff(r & 15, c & 31) + 16 LD (r >> 4) + 256 (c >> 5) (the XOR
 // takes row bits 1 and 3): the callers pass that split (rlo = r & 15, clo =
 // c & 31, rblk = r >> 4, cblk = c >> 5) so each lane keeps one base per
@@ -81,51 +75,27 @@ __device__ __forceinline__ int hsplit(int rlo, int clo, int rblk, int cblk) {
     return hoff<LD>(rlo, clo) + 16 * LD * rblk + 256 * cblk;
 }
 
-// img[r0 + 8(l>>4) + e][c0 + (l&15)], e = 0..7 (two ds_read_b64_tr_b16);
+// img[r0 + 8(l>>4) + e][c0 + (l&15)], e = 0..7 (frag_tr2, learn_img.hpp);
 // r0 % 32 == 0, c0 % 16 == 0.
 template <int LD = H>
 __device__ __forceinline__ half8 frag_tr_h(const h16 *img, int r0, int c0) {
     const int l = threadIdx.x & 63, i = l & 15, g = l >> 4;
     const h16 *p0 = img + hsplit<LD>(8 * (g & 1) + (i >> 2), (c0 & 16) + 4 * (i & 3), g >> 1, 0) +
                     (16 * LD * (r0 >> 4) + 256 * (c0 >> 5));
-    v4s t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)p0);
-    v4s t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(p0 + 128));
-    half8 r;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        r[e] = __builtin_bit_cast(h16, (short)t0[e]);
-        r[e + 4] = __builtin_bit_cast(h16, (short)t1[e]);
-    }
-    return r;
+    return frag_tr2(p0, 128);
 }
 
 // frag_tr_h at this lane's first-read address p0 (the caller's hsplit base
 // plus a compile-time offset).
 __device__ __forceinline__ half8 frag_tr_p(const h16 *p0) {
-    v4s t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)p0);
-    v4s t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(p0 + 128));
-    half8 r;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        r[e] = __builtin_bit_cast(h16, (short)t0[e]);
-        r[e + 4] = __builtin_bit_cast(h16, (short)t1[e]);
-    }
-    return r;
+    return frag_tr2(p0, 128);
 }
 
 // Same, plain row-major [rows][ld] image (the DQ image, ld 16).
 __device__ __forceinline__ half8 frag_tr(const h16 *img, int ld, int r0, int c0) {
     const int l = threadIdx.x & 63, i = l & 15, g = l >> 4;
     const h16 *p0 = img + (r0 + 8 * g + (i >> 2)) * ld + c0 + 4 * (i & 3);
-    v4s t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)p0);
-    v4s t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(p0 + 4 * ld));
-    half8 r;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        r[e] = __builtin_bit_cast(h16, (short)t0[e]);
-        r[e + 4] = __builtin_bit_cast(h16, (short)t1[e]);
-    }
-    return r;
+    return frag_tr2(p0, 4 * ld);
 }
 
 // ---------------------------------------------------------------- the network in LDS
@@ -373,9 +343,6 @@ __device__ __forceinline__ void fwd_tiles(const Net &N, const half8 (&bx)[NT][3]
 // ---------------------------------------------------------------- pass 1: S'
 // LDS: both nets (2 x 58,896 B) + per wave: rewards f64 [128], ring slots
 // [128], transition word (a | done << 8) [128], z-scored rewards f32 [128].
-#ifndef SH_B4
-#define SH_B4 0  // 1: the barrier between an agent's dW1 and the next agent's L1 (round 5)
-#endif
 #ifndef NEXT_NT
 #define NEXT_NT 2  // 16-row tiles per weight read in k_shared_next
 #endif
@@ -447,38 +414,19 @@ __global__ void __launch_bounds__(64 * NEXT_WAVES, 1) k_shared_next(dmdqn_learn_
         r64[l + 64] = __longlong_as_double((long long)(((unsigned long long)m1.w << 32) | m1.z));
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS writes landed
         __builtin_amdgcn_wave_barrier();
-        // z-score of the batch rewards in numpy's pairwise order (learn_h16.hpp
-        // zscore): 8 partial sums of 16
+        // z-score of the batch rewards (learn_rules.hpp: the pieces of zscore, at
+        // wave level -- shuffles in place of the LDS cells and barriers)
         double part = 0.0;
-        if (l < 8) {
-            part = r64[l];
-            for (int k = 1; k < 16; k++) part = __dadd_rn(part, r64[8 * k + l]);
-        }
+        if (l < 8) part = zs_part_sum(r64 + l);
         double p[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) p[k] = __shfl(part, k);
-        const double mean = __ddiv_rn(__dadd_rn(0.0, __dadd_rn(__dadd_rn(__dadd_rn(p[0], p[1]),
-                                                                         __dadd_rn(p[2], p[3])),
-                                                               __dadd_rn(__dadd_rn(p[4], p[5]),
-                                                                         __dadd_rn(p[6], p[7])))),
-                                      128.0);
+        const double mean = zs_mean(p);
         part = 0.0;
-        if (l < 8) {
-            for (int k = 0; k < 16; k++) {
-                const double d = __dsub_rn(r64[8 * k + l], mean);
-                const double sq = __dmul_rn(d, d);
-                part = k == 0 ? sq : __dadd_rn(part, sq);
-            }
-        }
+        if (l < 8) part = zs_part_sqdev(r64 + l, mean);
 #pragma unroll
         for (int k = 0; k < 8; k++) p[k] = __shfl(part, k);
-        const double sd = __dadd_rn(
-            __dsqrt_rn(__ddiv_rn(__dadd_rn(0.0, __dadd_rn(__dadd_rn(__dadd_rn(p[0], p[1]),
-                                                                    __dadd_rn(p[2], p[3])),
-                                                          __dadd_rn(__dadd_rn(p[4], p[5]),
-                                                                    __dadd_rn(p[6], p[7])))),
-                                 128.0)),
-            1e-8);
+        const double sd = zs_std(p);
         // the z-scored rewards of rows l and l + 64, by every lane (one f64
         // division per lane and row instead of per row in each tile's epilogue)
         rnf[l] = (float)__ddiv_rn(__dsub_rn(r64[l], mean), sd);
@@ -502,13 +450,10 @@ __global__ void __launch_bounds__(64 * NEXT_WAVES, 1) k_shared_next(dmdqn_learn_
 #pragma unroll
                 for (int n = 0; n < NEXT_NT; n++) {
                     const int b = RT * rp + 16 * n + i;
-                    // Double-DQN target (dqn_agent.py:342-347, first max on
-                    // ties), each op rounded on its own as TF's
-                    int best = 0;
-                    float bq = qo[n][0];
-                    if (qo[n][1] > bq) { best = 1; bq = qo[n][1]; }
-                    if (qo[n][2] > bq) { best = 2; bq = qo[n][2]; }
-                    if (qo[n][3] > bq) { best = 3; }
+                    // Double-DQN target (learn_rules.hpp: first_max4; y must match
+                    // the bits of td_target -- this file is built with contraction
+                    // off, and mul_rn's pinned product reorders the epilogue)
+                    const int best = first_max4(qo[n][0], qo[n][1], qo[n][2], qo[n][3]);
                     const float tq = best == 0 ? qt[n][0] : best == 1 ? qt[n][1] : best == 2 ? qt[n][2] : qt[n][3];
                     const uint32_t m = tw[b];
                     const float rn = rnf[b];
@@ -526,7 +471,9 @@ __global__ void __launch_bounds__(64 * NEXT_WAVES, 1) k_shared_next(dmdqn_learn_
 }
 
 // ---------------------------------------------------------------- pass 2: gradients
-// Per-row loss term and dL/dq (common.hpp loss_term), rounded as TF's ops.
+// Per-row loss term and dL/dq, rounded as TF's ops: must match the bits of
+// loss_term (learn_rules.hpp).  Kept in this form for k_shared_grad4's generated
+// code: loss_term's mul_rn pins a value and renumbers the kernel's registers.
 __device__ __forceinline__ void row_loss(int kind, float diff, float &term, float &dq) {
 #pragma clang fp contract(off)
     if (kind == DMDQN_LOSS_HUBER) {
@@ -976,10 +923,9 @@ __global__ void __launch_bounds__(512, 1) k_shared_grad4(dmdqn_learn_args a, con
         yv = yn;
         avl = an;
         SH_STAMP(agent, 6, threadIdx.x);
-#if SH_B4
-        __syncthreads();  // B4: the images are rewritten by the next agent
-#endif
-        // (round 6: no barrier here.  What the next agent's L1 writes, H1's
+        // (round 6: no barrier here; round 5's B4 between an agent's dW1 and the
+        // next agent's L1 is retired, DESIGN §6: tools/build_rev.py 2521462
+        // <name> -DSH_B4=1.  What the next agent's L1 writes, H1's
         // own columns, every wave last read in dW2 -- before the pair barrier
         // above; L1 reads the other X buffer, which RQ committed before B3.
         // The later writes wait for B1: L2's H2 columns, which dW1 reads; RQ's
@@ -1028,9 +974,6 @@ __global__ void __launch_bounds__(512, 1) k_shared_grad4(dmdqn_learn_args a, con
 }
 
 }  // namespace g4
-
-
-
 
 }  // namespace shk
 

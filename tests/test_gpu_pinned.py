@@ -332,11 +332,14 @@ def test_learn_h16_huber_loss_and_gradient(precision):
         assert np.corrcoef(p_g[j] - p0[j], p1 - p0[j])[0, 1] > 0.97
 
 
-@pytest.mark.parametrize("precision", ["fp32", "fp16", "bf16"])
+@pytest.mark.parametrize("precision", ["fp32", "fp16", "bf16", "fp16-shared"])
 def test_device_zscore_bit_exact(precision):
     """The z-scored rewards each learn kernel used (rn_out) equal numpy's
-    (rewards - mean) / (std + 1e-8) of dqn_agent.py:66-69 bit for bit."""
-    ag = BatchedDQN(2, 3, AgentConfig(replay_buffer_size=400, seed=2, precision=precision))
+    (rewards - mean) / (std + 1e-8) of dqn_agent.py:66-69 bit for bit.
+    fp16-shared: the shared-network learn (its S' pass scores at wave level)."""
+    precision, _, shared = precision.partition("-")
+    ag = BatchedDQN(2, 3, AgentConfig(replay_buffer_size=400, seed=2, precision=precision,
+                                      shared_params=bool(shared)))
     rng = np.random.RandomState(4)
     _fill(ag, 300, rng)
     ag.rn_out = torch.zeros((ag.NA, 128), dtype=torch.float32, device=DEV)

@@ -1,5 +1,6 @@
-"""CPU checks of the LDS image addressing of the C5 gradient pass
-(dmdqn_amd/csrc/learn_shared.hip): every call site of hsplit computes exactly
+"""CPU checks of the LDS image addressing of the C5 gradient pass (hoff:
+dmdqn_amd/csrc/learn_img.hpp; hsplit and its call sites:
+dmdqn_amd/csrc/learn_shared.hip): every call site of hsplit computes exactly
 hoff(r, c) for the (row, column) it means, and the images stay bijective.  A
 wrong split reads another wave's columns (a race, not a fault), so it is
 checked here on every lane / index the kernel uses, not by a spot check."""
