@@ -45,6 +45,9 @@ SIGNATURES = {
     "dmdqn_event_destroy": [vp],
     "dmdqn_stream_probe": [vp, vp, C.c_size_t, i32, vp],
     "dmdqn_device_lds_per_cu": [i32, vp],
+    "dmdqn_pbt_score": [vp, i32, i32, vp, vp],
+    "dmdqn_pbt_select": [vp, i32, i32, vp, vp, vp],
+    "dmdqn_pbt_exchange": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
 }
 
 

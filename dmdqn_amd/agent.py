@@ -27,6 +27,12 @@ writes the raw transition into a staging ring of n_step slots and one more
 launch (dmdqn_replay_nstep_commit) stores the n-step transition of the oldest
 staged one into the replay ring; the learn is unchanged and bootstraps with
 gamma^n_step, and its batch z-score runs over the stored returns.
+
+Population-based training: with AgentConfig.pbt the replicas are a population.
+pbt_score() adds a step's reward to each replica's fitness; at a round
+pbt_select() ranks them, pbt_exchange() copies the best replicas' nets and Adam
+slots over the worst ones' in place and pbt_explore() perturbs the copied
+per-agent hyperparameters (the Trainer calls all four).
 """
 import ctypes as C
 import itertools
@@ -305,6 +311,108 @@ def sweep_variants(cfg):
     return [dict(base, **dict(zip(sweep, combo))) for combo in itertools.product(*lists)]
 
 
+PBT_KEYS = ("interval", "truncation", "perturb", "bounds", "seed")
+PBT_PERTURB = {"learning_rate": [0.8, 1.25]}
+PBT_BOUNDS = {"learning_rate": [1e-6, 1e-1], "gamma": [0.5, 0.9999], "tau": [1e-4, 1.0]}
+
+
+def normalize_pbt(pbt):
+    """AgentConfig.pbt with its defaults filled in, or None: {interval,
+    truncation, perturb {key: [factors]}, bounds {key: [lo, hi]} for every
+    sweep key, seed}, the two inner dicts in SWEEP_KEYS order.  ValueError on
+    an unknown key, a missing or non-positive interval, a truncation that is
+    not a finite number, a perturb / bounds key that is not a sweep key, an
+    empty factor list, a factor that is not finite and > 0, a bound that is not
+    a finite [lo, hi] with lo <= hi, or a negative seed."""
+    if pbt is None:
+        return None
+    if not isinstance(pbt, dict):
+        raise ValueError(f"pbt must be a dict, got {type(pbt).__name__}")
+    for k in pbt:
+        if k not in PBT_KEYS:
+            raise ValueError(f"pbt key {k!r}: only {', '.join(PBT_KEYS)} are known")
+
+    def integer(name, lo):
+        v = pbt.get(name)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < lo:
+            raise ValueError(f"pbt[{name!r}] must be an integer >= {lo}, got {v!r}")
+        return int(v)
+    if "interval" not in pbt:
+        raise ValueError("pbt needs 'interval' (trainer steps between rounds)")
+    out = {"interval": integer("interval", 1)}
+    try:
+        out["truncation"] = float(pbt.get("truncation", 0.25))
+    except (TypeError, ValueError):
+        raise ValueError(f"pbt['truncation'] must be a number, got {pbt['truncation']!r}") from None
+    if not math.isfinite(out["truncation"]):
+        raise ValueError(f"pbt['truncation'] must be finite, got {pbt['truncation']!r}")
+    for name, default in (("perturb", PBT_PERTURB), ("bounds", PBT_BOUNDS)):
+        given = pbt.get(name, default)
+        if not isinstance(given, dict):
+            raise ValueError(f"pbt[{name!r}] must be a dict of lists, got {given!r}")
+        for k in given:
+            if k not in SWEEP_KEYS:
+                raise ValueError(f"pbt[{name!r}] key {k!r}: only {', '.join(SWEEP_KEYS)}")
+        lists = {}
+        for k in SWEEP_KEYS:
+            if k not in given and name == "perturb":
+                continue
+            try:
+                vals = [float(v) for v in given.get(k, PBT_BOUNDS[k])]
+            except (TypeError, ValueError):
+                raise ValueError(f"pbt[{name!r}][{k!r}] must be a list of numbers, "
+                                 f"got {given[k]!r}") from None
+            if not all(math.isfinite(v) for v in vals):
+                raise ValueError(f"pbt[{name!r}][{k!r}]: {vals!r} must be finite")
+            if name == "perturb" and (not vals or min(vals) <= 0.0):
+                raise ValueError(f"pbt['perturb'][{k!r}]: {vals!r} must be a non-empty list of "
+                                 "factors > 0")
+            if name == "bounds" and (len(vals) != 2 or vals[0] > vals[1]):
+                raise ValueError(f"pbt['bounds'][{k!r}]: {vals!r} must be [lo, hi] with lo <= hi")
+            lists[k] = vals
+        out[name] = lists
+    out["seed"] = integer("seed", 0) if "seed" in pbt else 0
+    return out
+
+
+def pbt_truncated(truncation, num_envs):
+    """n = floor(truncation * E), the replicas replaced per round."""
+    return int(math.floor(float(truncation) * int(num_envs)))
+
+
+def check_pbt(cfg, num_envs):
+    """normalize_pbt(cfg.pbt) checked against the run, plus "n" (the replicas
+    replaced per round), or None.  ValueError (before any device work) when
+    n < 1 or 2 n > E (winners and losers must be disjoint: that is what makes
+    the in-place exchange free of races), with shared_params (one net has no
+    population), or when tau is perturbed while the run's tau is 0 (hard-only
+    and soft nets cannot share a launch)."""
+    pbt = normalize_pbt(cfg.pbt)
+    if pbt is None:
+        return None
+    if cfg.shared_params:
+        raise ValueError("pbt needs independent networks: shared_params trains one net, "
+                         "which has no population")
+    n = pbt_truncated(pbt["truncation"], num_envs)
+    if n < 1 or 2 * n > int(num_envs):
+        raise ValueError(f"pbt: truncation {pbt['truncation']!r} of {num_envs} replicas replaces "
+                         f"n = {n}; need 1 <= n and 2 n <= E")
+    if "tau" in pbt["perturb"] and float(cfg.tau) == 0.0 and "tau" not in (cfg.sweep or {}):
+        raise ValueError("pbt perturbs tau but the run's tau is 0 (hard target updates only)")
+    return dict(pbt, n=n)
+
+
+def pbt_config_list(pbt):
+    """normalize_pbt(pbt) as nested lists of plain values, key order fixed: what
+    a checkpoint stores and compares (None stays None)."""
+    p = normalize_pbt(pbt)
+    if p is None:
+        return None
+    return [["interval", p["interval"]], ["truncation", p["truncation"]],
+            ["perturb", [[k, list(v)] for k, v in p["perturb"].items()]],
+            ["bounds", [[k, list(v)] for k, v in p["bounds"].items()]], ["seed", p["seed"]]]
+
+
 def variant_assignment(n_variants, num_envs, env_offset=0):
     """int64 [num_envs]: replica with global index g = env_offset + e runs
     variant g % G, so a rank of a sharded run holds the variants a
@@ -401,6 +509,16 @@ class AgentConfig:
     # most replay_buffer_size; 1 = the reference's one-step transitions (no
     # staging ring, no extra launch).  Not a sweep key.
     n_step: int = 1
+    # population-based training across the env replicas (normalize_pbt): every
+    # `interval` trainer steps the n = floor(truncation * E) replicas of lowest
+    # fitness (the reward summed over the window) take over the nets, Adam
+    # slots and hyperparameters of the n best, and each copied value of a
+    # `perturb` key is multiplied by a factor drawn from its list and clipped
+    # to `bounds`.  {"interval": 500} alone: truncation 0.25, perturb
+    # {"learning_rate": [0.8, 1.25]}, seed 0.  A perturbed key is per agent like
+    # a swept one (starting from the scalar when not swept).  None = off:
+    # nothing is allocated or launched.
+    pbt: Optional[dict] = None
 
     @classmethod
     def from_dict(cls, d):
@@ -433,10 +551,14 @@ class BatchedDQN:
     OUT_BUFS = 3
 
     def __init__(self, num_envs, n_agents, cfg: AgentConfig = None, device="cuda",
-                 env_seeds=None, init_weights=None, streams=None, variant_of_env=None):
+                 env_seeds=None, init_weights=None, streams=None, variant_of_env=None,
+                 env_offset=0):
         self.cfg = cfg = cfg or AgentConfig()
         # the sweep's variants and each replica's (refusals before any device work)
         self.variants = sweep_variants(cfg)
+        # population-based training: the checked config (+ "n"), or None
+        self.pbt = check_pbt(cfg, num_envs)
+        self.env_offset = int(env_offset)  # global index of replica 0 (the explore draws' key)
         self.n_step = check_n_step(cfg.n_step, cfg.replay_buffer_size)
         # what the learn takes for gamma: gamma^n_step (n_step 1: gamma itself)
         self.gamma_n = nstep_gamma(cfg.gamma, self.n_step)
@@ -580,7 +702,9 @@ class BatchedDQN:
         self.variant_of_env = torch.as_tensor(voe)
         self._variant_of_agent = self.variant_of_env.repeat_interleave(n_agents).to(dev)
         self.hp_lr = self.hp_gamma = self.hp_tau = self.hp_omt = None
-        swept = cfg.sweep or {}
+        # (a key population-based training perturbs is per agent like a swept
+        # one; not swept, every variant holds the scalar it starts from)
+        swept = set(cfg.sweep or {}) | set(self.pbt["perturb"] if self.pbt else ())
         per_agent = np.repeat(voe, n_agents)
 
         def column(values):
@@ -599,6 +723,17 @@ class BatchedDQN:
             self.hp_tau = column([c[0] for c in consts])
             self.hp_omt = column([c[1] for c in consts])
         self._last_factors = (1.0, 1.0)
+        # population-based training: the master values of every per-agent key
+        # (host f64 [E], SWEEP_KEYS order), the window's fitness (device f64
+        # [E]) and the index of the next round; nothing without cfg.pbt
+        self.pbt_values = self.fitness = None
+        self.pbt_round = 0
+        if self.pbt is not None:
+            self.pbt_values = {k: np.asarray([self.variants[i][k] for i in voe], dtype=np.float64)
+                               for k in SWEEP_KEYS if k in swept}
+            self.fitness = torch.zeros(num_envs, dtype=torch.float64, device=dev)
+            self._pbt_rank = torch.empty(num_envs, dtype=torch.int32, device=dev)
+            self._pbt_src = torch.empty(num_envs, dtype=torch.int32, device=dev)
 
     @property
     def swept(self):
@@ -850,7 +985,11 @@ class BatchedDQN:
         per sweep variant, reduced over the agents of the variant's replicas,
         plus "variant" (its index), its learning_rate / gamma / tau and "envs"
         (how many replicas run it; the scalars are None for a variant without
-        replicas).  Syncs."""
+        replicas).  Under population-based training by_variant raises
+        ValueError: the variants dissolve at the first round.  Syncs."""
+        if by_variant and self.pbt is not None:
+            raise ValueError("learn_metrics(by_variant=True): population-based training moves "
+                             "the replicas off the sweep's variants (see pbt_values)")
         qs = self.qstats.double()
         n = float(self.cfg.batch_size * N_ACTIONS)
         mean = qs[:, 0] / n
@@ -952,6 +1091,101 @@ class BatchedDQN:
             check_tau(self.cfg.tau if tau is None else tau, allow_zero=False))
         self._ops.target_soft_update(self.params, self.target, self.target_h,
                                      PRECISIONS[self.cfg.precision], float(tau_f), float(omt_f))
+
+    # -------------------------------------------------------------- population-based training
+    def _pbt_on(self):
+        if self.pbt is None:
+            raise ValueError("population-based training is off (AgentConfig.pbt is None)")
+
+    def pbt_score(self, reward):
+        """fitness[e] += the step's reward f64 [E, A] summed over the junctions
+        in order (dmdqn_pbt_score), on the current stream."""
+        self._pbt_on()
+        self._ops.pbt_score(reward, self.fitness)
+
+    def pbt_select(self):
+        """Truncation selection on the window's fitness (dmdqn_pbt_select):
+        (src, rank) as host int32 [E] arrays -- replica e copies replica
+        src[e] (itself for all but the n worst), rank 0 is the best.  One
+        device-to-host copy; syncs the current stream."""
+        self._pbt_on()
+        self._ops.pbt_select(self.fitness, self.pbt["n"], self._pbt_rank, self._pbt_src)
+        both = torch.stack([self._pbt_src, self._pbt_rank]).cpu().numpy()
+        return both[0].copy(), both[1].copy()
+
+    def _pbt_src_checked(self, src):
+        src = np.asarray(src, dtype=np.int64).reshape(-1)
+        if src.shape != (self.E,) or (src < 0).any() or (src >= self.E).any():
+            raise ValueError(f"src must hold {self.E} replica indices in [0, {self.E})")
+        if (src[src] != src).any():
+            # a source that is itself overwritten would race its own copy
+            raise ValueError("src: every source must be a fixed point (src[src[e]] == src[e])")
+        return src
+
+    def pbt_exchange(self, src):
+        """Exploit: for every replica e with src[e] != e, the params, target,
+        Adam m / v rows (and the 16-bit target shadow's) of its agents are
+        overwritten, as bits, with those of replica src[e]'s (dmdqn_pbt_exchange,
+        in place, on the current stream).  src: host [E]; every source must be
+        a fixed point.  Replay rings, staging rings, RNG streams and the env
+        stay each replica's own."""
+        self._pbt_on()
+        src = self._pbt_src_checked(src)
+        self._pbt_src.copy_(torch.as_tensor(src.astype(np.int32)))
+        self._ops.pbt_exchange(self._pbt_src, self.A, self.params, self.target, self.adam_m,
+                               self.adam_v, self.target_h)
+
+    def pbt_explore(self, src):
+        """Explore, round self.pbt_round: every copied replica (src[e] != e)
+        takes its source's value of each per-agent key, a perturbed key's
+        multiplied by a factor drawn from its list and clipped to its bounds;
+        the draws come from RandomState([seed, round, env_offset]), one
+        randint(0, len(factors), size=E) per perturbed key in SWEEP_KEYS order
+        (drawn for every replica, copied or not).  The per-agent device arrays
+        are then rebuilt from pbt_values (on the current stream), so a clone
+        computes what a scalar run with its new values computes."""
+        self._pbt_on()
+        src = self._pbt_src_checked(src)
+        p = self.pbt
+        rs = np.random.RandomState(np.array([p["seed"], self.pbt_round, self.env_offset],
+                                            dtype=np.uint32))
+        for k in SWEEP_KEYS:
+            if k in p["perturb"]:
+                factors = p["perturb"][k]
+                lo, hi = p["bounds"][k]
+                c = rs.randint(0, len(factors), size=self.E)
+            v = self.pbt_values.get(k)
+            if v is None:
+                continue
+            for e in np.nonzero(src != np.arange(self.E))[0]:
+                x = float(v[src[e]])
+                if k in p["perturb"]:
+                    x = min(max(x * factors[c[e]], lo), hi)
+                v[e] = x
+        self._pbt_upload()
+
+    def _pbt_upload(self):
+        """The per-agent device arrays from pbt_values, by the formulas that
+        built them (in place: the learn kernels re-read them every launch)."""
+        def put(dst, values, dtype):
+            host = np.repeat(np.asarray(values, dtype=dtype), self.A)
+            dst.copy_(torch.as_tensor(host))
+        pv = self.pbt_values
+        if "learning_rate" in pv:
+            put(self.hp_lr, pv["learning_rate"], np.float32)
+        if "gamma" in pv:
+            put(self.hp_gamma, [nstep_gamma(g, self.n_step) for g in pv["gamma"]], np.float32)
+            if self.nstep_gamma_a is not None:
+                put(self.nstep_gamma_a, pv["gamma"], np.float64)
+        if "tau" in pv:
+            consts = [soft_update_consts(t) for t in pv["tau"]]
+            put(self.hp_tau, [c[0] for c in consts], np.float32)
+            put(self.hp_omt, [c[1] for c in consts], np.float32)
+
+    def pbt_population(self):
+        """{key: [min, median, max]} of pbt_values, per per-agent key."""
+        return {k: [float(np.min(v)), float(np.median(v)), float(np.max(v))]
+                for k, v in self.pbt_values.items()}
 
     # -------------------------------------------------------------- weights
     def keras_params(self, which="params"):

@@ -72,6 +72,8 @@ KERNEL_SOURCES = {
     "learn": ["learn.hip", "learn_f16.hip", "learn_bf16.hip", "learn_h16.hpp", "learn_shared.hip",
               "learn_rules.hpp", "learn_img.hpp", "qnet_layout.hpp", "common.hpp"],
     "sim": ["sim.hip", "sim.hpp", "observe.hpp", "common.hpp"],
+    # population-based training (score / select / exchange): off the step's path
+    "pbt": ["pbt.hip", "common.hpp"],
 }
 
 

@@ -16,6 +16,8 @@ needs, so that load + K steps reproduces an uninterrupted run bit-exactly
   env       lane rings, signal state, origin-queue cursors, stats, the clock,
             the last local state / observation (reward uses the pre-step state)
   trainer   episode / step counters and the current observation
+  pbt       population-based training: every replica's hyperparameter values,
+            the window's fitness, the round index and the rounds' log
 
 Everything is a tensor or a plain int / float / str, so the file loads with
 torch.load(weights_only=True).  Demand tables are NOT stored: they are rebuilt
@@ -43,7 +45,7 @@ _AGENT_TENSORS = ["params", "target", "adam_m", "adam_v", "np_state", "py_state"
 # derived state stale), so load() refuses it.
 _AGENT_FIXED = ["precision", "shared_params", "nn_layers", "replay_buffer_size", "batch_size",
                 "seed", "loss", "target_update_frequency", "count_env_steps", "replay_rows",
-                "ring_spare", "tau", "sweep", "n_step"]
+                "ring_spare", "tau", "sweep", "n_step", "pbt"]
 _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features", "cap_lane",
               "end_ms", "period_ms", "step_duration", "max_sim_time", "action_stride", "scenario",
               "actuated"]
@@ -53,9 +55,11 @@ _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features
 # arrays are rebuilt from it, not stored, so a resume under another sweep would
 # train the restored nets with other values.  n_step: a checkpoint saved before
 # n-step returns existed stored one-step transitions; the rings of another
-# n_step hold other returns and the learn another discount)
+# n_step hold other returns and the learn another discount.  pbt: a checkpoint
+# saved before population-based training existed ran without it; the rounds'
+# schedule, perturbation and draws are part of the run)
 _DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2,
-             "tau": 0.0, "sweep": None, "n_step": 1}
+             "tau": 0.0, "sweep": None, "n_step": 1, "pbt": None}
 _RING_TENSORS = ["s", "n", "a", "r", "d"]
 
 
@@ -84,6 +88,11 @@ def _cfg_dict(cfg):
         # [[key, [values]], ...]: the key order is part of the grid (it decides
         # which variant a replica runs), so it is compared too
         out["sweep"] = [[str(k), [float(x) for x in v]] for k, v in d["sweep"].items()]
+    if d.get("pbt") is not None:
+        # with its defaults filled in, as nested lists: {"interval": 500} and
+        # the same dict with the default truncation spelled out are one config
+        from .agent import pbt_config_list
+        out["pbt"] = pbt_config_list(d["pbt"])
     return out
 
 
@@ -119,6 +128,13 @@ def trainer_state(tr, include_replay=True):
         # window in flight) and its raw-store counter; n_step 1 adds no key
         st["nstep"] = {k: getattr(ag.stage, k).cpu() for k in _RING_TENSORS}
         st["nstep"]["total"] = int(ag.stage.total)
+    if ag.pbt is not None:
+        # population-based training: the master values behind the per-agent
+        # device arrays, the window's fitness so far, the next round's index
+        # and the rounds' log; no key without pbt
+        st["pbt"] = {"values": {k: torch.from_numpy(v.copy()) for k, v in ag.pbt_values.items()},
+                     "fitness": ag.fitness.cpu(), "round": int(ag.pbt_round),
+                     "log": list(tr.pbt_log)}
     return st
 
 
@@ -184,6 +200,19 @@ def load(path, tr):
     if ag.stage is not None:
         for k in _RING_TENSORS:
             plan("nstep", getattr(ag.stage, k), st["nstep"][k], k)
+    # (pbt itself was compared above, so "pbt" is present exactly when this
+    # Trainer trains a population)
+    if (ag.pbt is None) != ("pbt" not in st):
+        raise ValueError("checkpoint and Trainer disagree on population-based training")
+    if ag.pbt is not None:
+        plan("pbt", ag.fitness, st["pbt"]["fitness"], "fitness")
+        if sorted(st["pbt"]["values"]) != sorted(ag.pbt_values):
+            raise ValueError(f"checkpoint pbt values {sorted(st['pbt']['values'])} != "
+                             f"{sorted(ag.pbt_values)} of this Trainer")
+        for k, v in st["pbt"]["values"].items():
+            if tuple(v.shape) != ag.pbt_values[k].shape or v.dtype != torch.float64:
+                raise ValueError(f"checkpoint pbt.values.{k} {v.dtype}{tuple(v.shape)} != "
+                                 f"float64{ag.pbt_values[k].shape}")
     # the restore writes on the caller's stream: order it after everything the
     # trainer queued on its side stream (the "env" schedule's side learn may
     # still be updating its agents' weights and Adam slots -- ADVICE r5)
@@ -200,6 +229,13 @@ def load(path, tr):
     ag.ring.total = c["ring_total"]
     if ag.stage is not None:
         ag.stage.total = int(st["nstep"]["total"])
+    if ag.pbt is not None:
+        # the per-agent device arrays are rebuilt from the stored values
+        for k, v in st["pbt"]["values"].items():
+            ag.pbt_values[k][:] = v.numpy()
+        ag._pbt_upload()
+        ag.pbt_round = int(st["pbt"]["round"])
+        tr.pbt_log = [dict(r) for r in st["pbt"]["log"]]
     ag._refresh_params_h()  # the 16-bit copies are derived from the f32 nets
     ag._refresh_target_h()
     tr.obs = st["obs"].to(env.device)

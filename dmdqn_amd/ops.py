@@ -35,6 +35,8 @@ ENTRY_POINTS = {
     "dmdqn_target_soft_update_hp": "target_soft_update_hp",
     "dmdqn_q_argmax": "q_argmax",
     "dmdqn_q_argmax_shared": "q_argmax",
+    "dmdqn_pbt_score": "pbt_score", "dmdqn_pbt_select": "pbt_select",
+    "dmdqn_pbt_exchange": "pbt_exchange",
 }
 
 TORCH_LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"libdmdqn_torch{_lib._SUFFIX}.so")

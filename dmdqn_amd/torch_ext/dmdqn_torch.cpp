@@ -602,8 +602,61 @@ void q_argmax(const Tensor &params, int64_t hidden, int64_t precision, const Ten
           "dmdqn_q_argmax");
 }
 
+// ---------------------------------------------------------------- population-based training
+void pbt_score(const Tensor &reward, Tensor &fitness) {
+    TORCH_CHECK(reward.dim() == 2, "reward must be [E, A]");
+    const int64_t E = reward.size(0), A = reward.size(1);
+    auto r = dptr<const double>(reward, at::kDouble, "reward");
+    auto f = dptr<double>(fitness, at::kDouble, "fitness", E);
+    TORCH_CHECK(fitness.device() == reward.device(), "fitness must be on the device of reward");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(reward.device());
+    check(dmdqn_pbt_score(r, int32_of(E, "E"), int32_of(A, "A"), f, stream_of(reward)),
+          "dmdqn_pbt_score");
+}
+
+void pbt_select(const Tensor &fitness, int64_t n, Tensor &rank, Tensor &src) {
+    const int64_t E = fitness.numel();
+    auto f = dptr<const double>(fitness, at::kDouble, "fitness");
+    auto r = dptr<int32_t>(rank, at::kInt, "rank", E);
+    auto s = dptr<int32_t>(src, at::kInt, "src", E);
+    TORCH_CHECK(rank.device() == fitness.device() && src.device() == fitness.device(),
+                "rank / src must be on the device of fitness");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(fitness.device());
+    check(dmdqn_pbt_select(f, int32_of(E, "E"), int32_of(n, "n"), r, s, stream_of(fitness)),
+          "dmdqn_pbt_select");
+}
+
+void pbt_exchange(const Tensor &src, int64_t A, Tensor &params, Tensor &target, Tensor &adam_m,
+                  Tensor &adam_v, const OptT &target_h) {
+    TORCH_CHECK(params.dim() == 2, "params must be [E * A, P]");
+    const int64_t E = src.numel(), NA = params.size(0), P = params.size(1);
+    TORCH_CHECK(A >= 1 && NA == E * A, "params holds ", NA, " rows, src ", E, " replicas of ", A);
+    auto sp = dptr<const int32_t>(src, at::kInt, "src");
+    auto p = dptr<float>(params, at::kFloat, "params");
+    auto t = dptr<float>(target, at::kFloat, "target", NA * P);
+    auto m = dptr<float>(adam_m, at::kFloat, "adam_m", NA * P);
+    auto v = dptr<float>(adam_v, at::kFloat, "adam_v", NA * P);
+    const int64_t Ph = target_h.has_value() ? target_h->numel() / NA : P;
+    TORCH_CHECK(!target_h.has_value() || (target_h->numel() % NA == 0 && Ph >= P),
+                "target_h must be [E * A, Ph] with Ph >= P");
+    TORCH_CHECK(target.device() == params.device() && adam_m.device() == params.device() &&
+                    adam_v.device() == params.device() && src.device() == params.device(),
+                "every tensor must be on the device of params");
+    TORCH_CHECK(!target_h.has_value() || target_h->device() == params.device(),
+                "target_h must be on the device of params");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    check(dmdqn_pbt_exchange(sp, int32_of(E, "E"), int32_of(A, "A"), int32_of(P, "P"),
+                             int32_of(Ph, "Ph"), p, t, m, v, h16ptr(target_h, "target_h"),
+                             stream_of(params)),
+          "dmdqn_pbt_exchange");
+}
+
 // Meta kernels: the ops only mutate their (a!) arguments, so tracing needs no
 // shape function beyond "nothing is returned".
+void pbt_score_meta(const Tensor &, Tensor &) {}
+void pbt_select_meta(const Tensor &, int64_t, Tensor &, Tensor &) {}
+void pbt_exchange_meta(const Tensor &, int64_t, Tensor &, Tensor &, Tensor &, Tensor &,
+                       const OptT &) {}
 void mt_seed_meta(Tensor &, const Tensor &, const std::string &) {}
 void mt_draw_u32_meta(Tensor &, int64_t, Tensor &) {}
 void act_meta(Tensor &, int64_t, double, int64_t, const OptT &, Tensor &, bool) {}
@@ -747,6 +800,11 @@ TORCH_LIBRARY(dmdqn, m) {
     // the greedy branch of select_action (dqn_agent.py:268-273)
     m.def("q_argmax(Tensor params, int hidden, int precision, Tensor obs, Tensor(a!) out, "
           "Tensor(b!)? q, bool shared) -> ()");
+    // population-based training across the replicas (nothing in the reference)
+    m.def("pbt_score(Tensor reward, Tensor(a!) fitness) -> ()");
+    m.def("pbt_select(Tensor fitness, int n, Tensor(a!) rank, Tensor(b!) src) -> ()");
+    m.def("pbt_exchange(Tensor src, int A, Tensor(a!) params, Tensor(b!) target, "
+          "Tensor(c!) adam_m, Tensor(d!) adam_v, Tensor(e!)? target_h) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
@@ -771,6 +829,9 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("target_soft_update", &target_soft_update);
     m.impl("target_soft_update_hp", &target_soft_update_hp);
     m.impl("q_argmax", &q_argmax);
+    m.impl("pbt_score", &pbt_score);
+    m.impl("pbt_select", &pbt_select);
+    m.impl("pbt_exchange", &pbt_exchange);
 }
 
 TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
@@ -795,4 +856,7 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("target_soft_update", &target_soft_update_meta);
     m.impl("target_soft_update_hp", &target_soft_update_hp_meta);
     m.impl("q_argmax", &q_argmax_meta);
+    m.impl("pbt_score", &pbt_score_meta);
+    m.impl("pbt_select", &pbt_select_meta);
+    m.impl("pbt_exchange", &pbt_exchange_meta);
 }

@@ -66,6 +66,13 @@ ring a learn samples lags the raw stores by n_step - 1 steps.  "none" (fused
 and fused=False) and "env" (with and without side_learn) run it, bit-identical
 to each other; "sample", "learn" and "full" raise ValueError for n_step > 1.
 
+Population-based training (AgentConfig.pbt): after every step the reward joins
+each replica's fitness on the caller's stream, and every `interval` steps a
+round runs there between quiesce() and join_streams(): select, the in-place
+exchange of the nets and Adam slots, explore (Trainer.pbt_log records it).
+"none" and "env" (with and without side_learn) run it, bit-identical to each
+other; the other schedules raise ValueError.
+
 What a step returns or exposes per step (obs, reward, loss, agent.actions,
 agent.idx) is fresh or double-buffered, so the caller may read it on its own
 stream between steps (under "env" with side_learn, read the loss through
@@ -76,10 +83,12 @@ it host-blocking (.cpu()), and call join_streams() after writing it.
 """
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from . import _lib
-from .agent import AgentConfig, BatchedDQN, check_n_step, sweep_variants, variant_assignment
+from .agent import (AgentConfig, BatchedDQN, check_n_step, check_pbt, sweep_variants,
+                    variant_assignment)
 from .env import EnvConfig, TrafficEnv
 
 
@@ -110,7 +119,15 @@ class Trainer:
         if check_n_step(agent_cfg.n_step, agent_cfg.replay_buffer_size) > 1 and overlap in (
                 "sample", "learn", "full", True):
             raise ValueError(f'n_step > 1 runs under overlap "none" or "env", not {overlap!r}')
-        self.env = TrafficEnv(env_cfg or EnvConfig(), device=device)
+        # population-based training (AgentConfig.pbt), checked like the sweep
+        # before any device work; its rounds run under the two schedules they
+        # are tested under, as n-step returns
+        env_cfg = env_cfg or EnvConfig()
+        if check_pbt(agent_cfg, env_cfg.num_envs) is not None and overlap not in (
+                "none", "env", False):
+            raise ValueError(f'pbt runs under overlap "none" or "env", not {overlap!r}')
+        self.pbt_log = []  # one dict per round (_pbt_round)
+        self.env = TrafficEnv(env_cfg, device=device)
         if overlap is True or overlap is False:
             overlap = "full" if overlap else "none"
         if overlap not in SCHEDULES:
@@ -128,7 +145,8 @@ class Trainer:
         # replica g = env_offset + e runs variant g % G of the sweep
         voe = variant_assignment(n_variants, self.env.E, self.env.cfg.env_offset)
         self.agent = BatchedDQN(self.env.E, self.env.A, agent_cfg, device=device,
-                                env_seeds=self.env.seeds, variant_of_env=voe)
+                                env_seeds=self.env.seeds, variant_of_env=voe,
+                                env_offset=self.env.cfg.env_offset)
         # overlap "learn": the sampler's LDS is what the shared learn's S' pass
         # leaves of a CU, so one sampler block runs beside each S' workgroup
         # (with the default four-blocks-per-CU budget the two serialise); the
@@ -195,11 +213,47 @@ class Trainer:
         also produce the metrics of dqn_agent.py:361-370 (agent.learn_metrics).
         Under the debug-bounds build (DMDQN_VARIANT=debug) every step ends with
         a device sync and the kernels' range checks."""
+        st = self._step(collect_stats)
+        if self.agent.pbt is not None:
+            self._pbt_after_step()
         if self._debug:
-            st = self._step(collect_stats)
             _lib.debug_check()
-            return st
-        return self._step(collect_stats)
+        return st
+
+    def _pbt_after_step(self):
+        """Population-based training, on the caller's stream: the step's reward
+        (already recorded to it under "env") joins the window's fitness; at
+        the end of a window (total_steps % interval == 0) a round runs if the
+        agents have learned, and the fitness restarts either way."""
+        agent = self.agent
+        agent.pbt_score(self.last_reward)
+        if self.total_steps % agent.pbt["interval"]:
+            return
+        if agent.learn_step_counter > 0:
+            self._pbt_round()
+        agent.fitness.zero_()
+
+    def _pbt_round(self):
+        """select -> exchange -> explore on the caller's stream, between
+        quiesce() (the side stream's env step, draws and side learn are done
+        with the nets) and join_streams() (its next work waits for the copy)."""
+        agent = self.agent
+        self.quiesce()
+        fit = agent.fitness.cpu().numpy()
+        src, rank = agent.pbt_select()
+        agent.pbt_exchange(src)
+        agent.pbt_explore(src)
+        key = np.where(fit != fit, -np.inf, fit)
+        order = np.argsort(rank)  # replicas, best first
+        self.pbt_log.append({
+            "round": agent.pbt_round, "step": self.total_steps,
+            "copied": [[int(e), int(s)] for e, s in enumerate(src) if s != e],
+            "best_env": int(order[0]),
+            "fitness_best": float(key[order[0]]), "fitness_median": float(np.median(key)),
+            "fitness_worst": float(key[order[-1]]),
+            "values": agent.pbt_population()})
+        agent.pbt_round += 1
+        self.join_streams()
 
     def _step(self, collect_stats):
         if self.overlap == "full":

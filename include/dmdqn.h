@@ -647,6 +647,52 @@ int dmdqn_adam_slabs(float *params, float *adam_m, float *adam_v, float *target,
                      float *grad, float scale, int n, float gscale, float alpha, float c1,
                      float c2, float eps, int sync, void *stream);
 
+/* ------------------------------------------------------------------ population-based training
+ * NOT in the reference (it builds every agent of a run from one config,
+ * train.py:110-121, and docs/improvements.md has no such item): these entry
+ * points replace nothing there.  The E env replicas of a launch are a
+ * population: each replica's A agents (agent = e * A + junction) train with
+ * their own hyperparameters (dmdqn_agent_hparams), a fitness is accumulated per
+ * replica, and at a round the worst n replicas take over the nets and Adam
+ * slots of the best n.  The explore half (perturbing the copied
+ * hyperparameters) is host work on the caller's side.  All three are
+ * deterministic and exact.  Refused on the host (DMDQN_EINVAL, before any
+ * launch): null pointers (target_h excepted), E / A / P / Ph out of range, n
+ * outside 1 .. E / 2. */
+
+/* fitness[e] += ((r[e][0] + r[e][1]) + ...) + r[e][A-1] for reward f64 [E][A]
+ * (a step's reward tensor) and fitness f64 [E]: f64 adds in junction order, no
+ * fma, one thread per replica.  E, A >= 1. */
+int dmdqn_pbt_score(const double *reward, int E, int A, double *fitness, void *stream);
+
+/* Truncation selection over fitness f64 [E], 2 <= E <= 65,536, 1 <= n <= E / 2.
+ * With f'[e] = fitness[e] (NaN taken as -inf):
+ *   rank[e] = #{x : f'[x] > f'[e]} + #{x < e : f'[x] == f'[e]}
+ * (int32 [E], a permutation: 0 = best, ties to the lower index), and
+ *   src[e] = e                             when rank[e] <  E - n,
+ *   src[e] = the x with rank[x] == E - 1 - rank[e]   otherwise
+ * (int32 [E]): the worst copies the best, the second worst the second best, so
+ * every source is a fixed point of src and has exactly one copy.  Two launches
+ * (ranks, then src); E * E compares, not for a hot path. */
+int dmdqn_pbt_select(const double *fitness, int E, int n, int32_t *rank, int32_t *src,
+                     void *stream);
+
+/* The in-place row exchange: for every replica e with s = src[e] != e and every
+ * junction j, the rows of agent s * A + j overwrite those of agent e * A + j in
+ * params, target, adam_m, adam_v (f32 [E * A][P]) and, when not NULL, target_h
+ * (16-bit [E * A][Ph]), copied as bits (16-B loads and stores only, no LDS, no
+ * staging buffer).  P % 4 == 0, Ph % 8 == 0 and 16-B aligned arrays, so every
+ * row starts on a 16-B boundary (P = 28,548 / 10,180 and Ph = 28,552 / 10,184
+ * do).  THE CALLER GUARANTEES that every source is a fixed point,
+ * src[src[e]] == src[e] (dmdqn_pbt_select's output is): a source row is then
+ * never written, which is what makes the copy free of races; src is device
+ * memory and is not checked here beyond 0 <= src[e] < E (any other value keeps
+ * the replica's rows).  Workgroups of a replica with src[e] == e exit at once.
+ * Moves 2 * (16 * P + 2 * Ph) bytes per copied agent. */
+int dmdqn_pbt_exchange(const int32_t *src, int E, int A, int P, int Ph, float *params,
+                       float *target, float *adam_m, float *adam_v, uint16_t *target_h,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,10 @@ class DQNAgent:
         self.agent_id = agent_id
         self.state_size = 89   # hard-coded as in the reference (A-16)
         self.action_size = 4
+        if config.get("pbt") is not None:
+            # population-based training evolves the replicas of one batched run
+            raise ValueError("config key 'pbt': one DQNAgent is one net, not a population "
+                             "(dmdqn_amd.trainer.Trainer runs it)")
         cfg = AgentConfig.from_dict(config)
         cfg.nn_layers = list(config.get("nn_layers", [64, 64]))  # reference default :127
         cfg.target_update_frequency = config.get("target_update_frequency", 1000)  # :124-126

@@ -15,6 +15,8 @@ stage for all agents (dmdqn_amd.trainer.Trainer) -- the throughput path.
   python -m src.scripts.train --batched --envs 1024 --grid 4x4 --episodes 1
   python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 \
       --sweep learning_rate=1e-4,5e-4,1e-3          # 3 variants in one run, ranked
+  python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 \
+      --sweep learning_rate=1e-4,1e-3 --pbt interval=200   # the best replicas replace the worst
   python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 --n_step 3
 """
 import argparse
@@ -134,6 +136,37 @@ def parse_sweep(items):
     return sweep
 
 
+def parse_pbt(spec, perturb_items=None):
+    """--pbt interval=500,truncation=0.25,seed=0 and the repeatable
+    --pbt_perturb KEY=f1,f2,... -> AgentConfig.pbt, or None without --pbt.
+    Only the syntax is checked here (and a key given twice, --pbt_perturb
+    without --pbt); the values where the config is used (agent.check_pbt)."""
+    if spec is None:
+        if perturb_items:
+            raise ValueError("--pbt_perturb needs --pbt")
+        return None
+    pbt = {}
+    for item in str(spec).split(","):
+        key, sep, val = item.partition("=")
+        key, val = key.strip(), val.strip()
+        if not sep or not key or not val:
+            raise ValueError(f"--pbt {spec!r}: expected interval=N[,truncation=F][,seed=N]")
+        if key not in ("interval", "truncation", "seed"):
+            raise ValueError(f"--pbt key {key!r}: interval, truncation or seed")
+        if key in pbt:
+            raise ValueError(f"--pbt {key} given twice")
+        try:
+            pbt[key] = float(val) if key == "truncation" else int(val)
+        except ValueError:
+            raise ValueError(f"--pbt {item!r}: not a number") from None
+    if perturb_items:
+        try:
+            pbt["perturb"] = parse_sweep(perturb_items)
+        except ValueError as e:
+            raise ValueError(str(e).replace("--sweep", "--pbt_perturb")) from None
+    return pbt
+
+
 def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenario=None,
                  save_dir=None, tau=0.0, target_update_frequency=None, n_step=1):
     dqn_agent.seed(seed)
@@ -174,7 +207,8 @@ def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenar
 
 def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, scenario=None,
                   shared=False, save_dir=None, resume=None, log_every=20, loss="mse",
-                  actuated=False, tau=0.0, target_update_frequency=None, sweep=None, n_step=1):
+                  actuated=False, tau=0.0, target_update_frequency=None, sweep=None, n_step=1,
+                  pbt=None):
     """E env replicas of the loop on the GPU.  The optional JSONL carries the
     reference's learn scalars (dqn_agent.py:361-370: loss, epsilon,
     q_values_mean / _std, action_distribution) and its per-step rewards with
@@ -184,12 +218,18 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     record then carries "variants" (per variant: its hyperparameters, replicas,
     total / smoothed total reward and learn scalars), the final line ranks the
     variants by smoothed total reward, and the exported Keras weights are those
-    of the best variant's first replica (the checkpoint holds them all)."""
+    of the best variant's first replica (the checkpoint holds them all).  pbt
+    (AgentConfig.pbt, parse_pbt): population-based training; the variants then
+    dissolve, so a record written at a round carries that round's pbt_log
+    entry, the final line a "pbt" block (rounds, copies, the best replica of
+    the last completed window with its values, the population's [min, median,
+    max] per key) instead of "variants", and the exported weights are that
+    best replica's."""
     from dmdqn_amd.agent import AgentConfig
     from dmdqn_amd.trainer import Trainer
     cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency, n_step=n_step))
     cfg.precision, cfg.seed, cfg.shared_params, cfg.loss = precision, seed, shared, loss
-    cfg.sweep = sweep
+    cfg.sweep, cfg.pbt = sweep, pbt
     tr = Trainer(EnvConfig(rows=rows, cols=cols, num_envs=envs, seed=seed, scenario=scenario,
                            actuated=actuated), cfg)
     from dmdqn_amd import checkpoint as CK
@@ -197,12 +237,14 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
         CK.load(resume, tr)
     out = open(metrics, "w") if metrics else None
     smooth_global, smooth_total = SmoothedValue(alpha=0.3), SmoothedValue(alpha=0.3)
-    variants = tr.agent.variants if sweep else []
+    variants = tr.agent.variants if sweep and not pbt else []
     smooth_variant = VariantSmoothedValues(alpha=0.3)
     t0 = time.perf_counter()
     steps = 0
     while tr.episode < episodes:
         log = out is not None and steps % log_every == 0
+        if out is not None and pbt and (tr.total_steps + 1) % tr.agent.pbt["interval"] == 0:
+            log = True  # the step a round may follow: its record carries the round
         if log:  # global reward of the PRE-step state (train.py:241, A-3)
             glob = -tr.env.local[..., :12].sum(dim=(1, 2), dtype=torch.float64)
         st = tr.step(collect_stats=log)
@@ -230,6 +272,8 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
                 for r, total_r, sm in zip(vrec, _host_values(vr), smooth_variant.get_values()):
                     r.update(total_reward=total_r, smooth_total_reward=sm)
                 rec["variants"] = vrec
+            if tr.pbt_log and tr.pbt_log[-1]["step"] == tr.total_steps:
+                rec["pbt"] = tr.pbt_log[-1]
             out.write(json.dumps(rec) + "\n")
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
@@ -241,6 +285,15 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
                                           smooth_variant.get_values() or [None] * len(variants))
         if final["variants"]:
             best_env = final["variants"][0]["first_env"]
+    if pbt:
+        ag = tr.agent
+        if tr.pbt_log:
+            best_env = tr.pbt_log[-1]["best_env"]
+        final["pbt"] = {"rounds": len(tr.pbt_log),
+                        "copies": sum(len(r["copied"]) for r in tr.pbt_log),
+                        "best_env": best_env,
+                        "best": {k: float(v[best_env]) for k, v in ag.pbt_values.items()},
+                        "population": ag.pbt_population()}
     print(json.dumps(final))
     if out:
         out.close()
@@ -330,15 +383,26 @@ def main():
                          "up to N rewards and the learn bootstraps with gamma^N (1..32; 1 = the "
                          "reference's one-step transitions); the last N-1 raw transitions of a "
                          "run are never stored")
+    ap.add_argument("--pbt", default=None, metavar="interval=N[,truncation=F][,seed=N]",
+                    help="batched only: population-based training across the env replicas -- "
+                         "every N steps the worst share F (default 0.25) of the replicas take "
+                         "over the nets and hyperparameters of the best, perturbed")
+    ap.add_argument("--pbt_perturb", action="append", default=None, metavar="KEY=f1,f2,...",
+                    help="with --pbt, repeatable: the factors a copied value of KEY "
+                         "(learning_rate, gamma or tau) is multiplied by, one drawn per copy "
+                         "(default learning_rate=0.8,1.25)")
     args = ap.parse_args()
     try:
         sweep = parse_sweep(args.sweep)
+        pbt = parse_pbt(args.pbt, args.pbt_perturb)
         from dmdqn_amd.agent import check_n_step
         check_n_step(args.n_step, AGENT_CONFIG["replay_buffer_size"])
     except ValueError as e:
         ap.error(str(e))
     if sweep and not args.batched:
         ap.error("--sweep needs --batched")
+    if pbt and not args.batched:
+        ap.error("--pbt needs --batched")
     logging.basicConfig(level=logging.INFO)
     rows, cols = (int(x) for x in args.grid.split("x"))
     scenario = args.scenario
@@ -349,7 +413,8 @@ def main():
     if args.batched:
         train_batched(args.episodes, rows, cols, args.envs, args.precision, args.seed, args.metrics,
                       scenario, args.shared, args.save_dir, args.resume, args.log_every, args.loss,
-                      args.actuated, args.tau, args.target_update_frequency, sweep, args.n_step)
+                      args.actuated, args.tau, args.target_update_frequency, sweep, args.n_step,
+                      pbt)
     else:
         train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir,
                      args.tau, args.target_update_frequency, args.n_step)
