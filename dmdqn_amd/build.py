@@ -71,7 +71,7 @@ EXTRA = os.environ.get("DMDQN_EXTRA_FLAGS", "").split()
 KERNEL_SOURCES = {
     "learn": ["learn.hip", "learn_f16.hip", "learn_bf16.hip", "learn_h16.hpp", "learn_shared.hip",
               "learn_rules.hpp", "learn_img.hpp", "qnet_layout.hpp", "common.hpp"],
-    "sim": ["sim.hip", "sim.hpp", "observe.hpp", "common.hpp"],
+    "sim": ["sim.hip", "sim.hpp", "sim_rules.hpp", "observe.hpp", "common.hpp"],
     # population-based training (score / select / exchange): off the step's path
     "pbt": ["pbt.hip", "common.hpp"],
 }

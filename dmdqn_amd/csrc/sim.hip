@@ -9,7 +9,9 @@
 //   getMinExpectedNumber() == 0 or t >= MAX_SIM_TIME -> done
 // The car-following model is IDM over per-lane vehicle rings (a NEW simulator,
 // not SUMO's Krauss: parity is against the C restatement in oracle/oracle_sim.c,
-// bit-exact, which needs -ffp-contract=off and the fixed operation order below).
+// bit-exact, which needs -ffp-contract=off and the fixed operation order of
+// sim_rules.hpp, where each rule of the passes below is defined once; this file
+// holds the storage forms that apply them and the fused prologue / epilogue).
 //
 // One substep (time t -> t+1), each pass data-parallel over lanes, passes
 // separated by block barriers:
@@ -30,21 +32,13 @@
 
 #include "common.hpp"
 #include "observe.hpp"
-#include "sim.hpp"
+#include "sim_rules.hpp"
 
 namespace dmdqn {
 
-__device__ __forceinline__ int last_slot(int head, int cnt, int cap) {
-    int s = head + cnt - 1;
-    return s >= cap ? s - cap : s;
-}
-
 // Positions of each lane held in the LDS image (kImg view); positions past it
 // stay in the HBM arrays.  4x4 at 12: a 38 KB image, four env blocks per CU.
-#ifndef DMDQN_LDS_POS
-#define DMDQN_LDS_POS 12
-#endif
-constexpr int kLdsPos = DMDQN_LDS_POS;
+constexpr int kLdsPos = 12;
 constexpr int kOvPre = 8;  // HBM positions pass C loads ahead
 
 // DT: element type of the destination rings -- int32 in HBM (dmdqn_sim.dst),
@@ -158,9 +152,6 @@ __device__ __forceinline__ QNext next_vehicle(const View &V, int p) {
     return QNext{(int)V.q_ids[p], (int)V.q_dst[p]};
 }
 
-#ifndef SIM_LANE_STRIDE_NT
-#define SIM_LANE_STRIDE_NT 1  // 0: the lane arrays NL apart, as before round 4 (A/B)
-#endif
 #ifdef DMDQN_SIM_PROFILE  // diagnostic build: per-pass ticks of thread 0 -> halt[env][0][0..7]
 #define SIM_PROF(i)                                                          \
     do {                                                                     \
@@ -170,55 +161,31 @@ __device__ __forceinline__ QNext next_vehicle(const View &V, int p) {
             prof_t = _n;                                                     \
         }                                                                    \
     } while (0)
+#define SIM_PROF_PARAMS , uint64_t *prof, uint64_t &prof_t  // substep's view of the kernel's timers
+#define SIM_PROF_ARGS , prof, prof_t
 #else
 #define SIM_PROF(i) do { } while (0)
+#define SIM_PROF_PARAMS
+#define SIM_PROF_ARGS
 #endif
 
-// The routing decision of a lane's front is a function of the lane and the
-// front's route word only (static topology): the movement m at the junction
-// ahead, the next edge e2 and the movement there (mv2 < 0: keep the lane
-// index).  Each thread keeps it for its first lane (l = tid) across substeps
-// and recomputes it only when the front's route word changes -- a front
-// waits at the stop line for many substeps.
-struct RouteCache {
-    int d0, m, e2, mv2;
-};
-
+// One substep on the LDS image or the global rings (View): the rules of
+// sim_rules.hpp over the view's storage.  rc: the route decision of the front
+// of the thread's first lane (l = tid), kept across substeps.
 template <bool kAct, typename View>
 __device__ __forceinline__ void substep(View &V, const Topo &T, const IdmK &P, int t,
-                                        QNext qn[QSLOTS], RouteCache &rc, uint64_t *prof,
-                                        uint64_t &prof_t) {
+                                        QNext qn[QSLOTS], RouteCache &rc SIM_PROF_PARAMS) {
     const dmdqn_sim &S = V.S;
     const int A = V.A, NL = V.NL, cap = V.cap;
     const int tid = threadIdx.x, nt = blockDim.x;
 
-    // ---- TL: natural phase advance (fixed durations; actuated gap-out of
-    // phase 0 in actuated mode: after minDur, once no vehicle has been over a
-    // detector of the phase's green lanes for more than max_gap, or at maxDur)
-    for (int a = tid; a < A; a += nt) {
-        const int p = V.phase[a], el = t - V.ts[a];
-        bool sw;
-        if (S.actuated && p == 0) {
-            constexpr uint32_t gl = green_lanes(0x11BB);  // green_mask(0)
-            int last = kNoDetection;
-#pragma unroll
-            for (int k = 0; k < 12; k++)
-                if ((gl >> k) & 1u) last = max(last, V.last_det[a * 12 + k]);
-            sw = el >= kActMax || (el >= kActMin && (float)(t - last) > P.max_gap);
-        } else {
-            sw = el >= phase_dur(p);
-        }
-        if (sw) {
-            V.phase[a] = (p + 1) % 12;
-            V.ts[a] = t;
-        }
-    }
+    // ---- TL: natural phase advance
+    for (int a = tid; a < A; a += nt)
+        tl_advance(V.phase[a], V.ts[a], t, S.actuated, V.last_det + a * 12, P);
     __syncthreads();
     SIM_PROF(0);
 
-    // ---- A: front vehicles decide.  One IDM evaluation per front (free
-    // road: no interaction term; green with a vehicle on the target lane: that
-    // vehicle; red/yellow: the stop line), its inputs chosen by selects.
+    // ---- A: front vehicles decide (route_decide, front_move)
     for (int l = tid; l < NL; l += nt) {
         V.gfrom[l] = -1;
         int n = V.cnt[l];
@@ -239,37 +206,19 @@ __device__ __forceinline__ void substep(View &V, const Topo &T, const IdmK &P, i
             f0 = V.ld(base + h0);
             d0 = V.dst[base + h0];
         }
-        const float x0 = f0.x, v0 = f0.y;
         const float len = lane_length(T, e);
-        // exit edge or last edge: free road
-        const bool free_road = e >= 4 * A || on_final_edge(d0, e);
+        const bool free_road = on_free_road(T, e, d0);
         bool green = false, lead = false;
         int tl = -1;
         float xl = 0.0f, vl = 0.0f;
         if (!free_road) {
-            const int aj = e >> 2, d = e & 3, h = opp(d);
-            int m, e2, mv2;
-            if (l == tid && rc.d0 == d0) {
-                m = rc.m;
-                e2 = rc.e2;
-                mv2 = rc.mv2;
-            } else {
-                const int o = out_dir(T, aj, h, d0);
-                m = movement(h, o);
-                DMDQN_DBG(T.nbr(aj, o) >= 0 || T.exit_id[aj * 4 + o] >= 0, DBG_SIM_EDGE);
-                e2 = next_edge(T, aj, o);
-                // lane_for: connections keep the lane index onto exit / final edges
-                const int w2 = route_advance(d0);
-                mv2 = -1;
-                if (!(e2 >= 4 * A || on_final_edge(w2, e2))) {
-                    const int h2 = opp(e2 & 3);
-                    mv2 = movement(h2, out_dir(T, e2 >> 2, h2, w2));
-                }
-                if (l == tid) rc = RouteCache{d0, m, e2, mv2};
+            int pk = rc.pk;
+            if (l != tid || rc.d0 != d0) {
+                pk = route_decide(T, e, d0);
+                if (l == tid) rc = RouteCache{d0, pk};
             }
-            const int k2 = mv2 < 0 ? kf : lane_for_move(mv2, e2, V.cnt);
-            tl = e2 * 3 + k2;
-            green = (green_mask(V.phase[aj]) >> (d * 4 + m)) & 1;
+            tl = route_target(pk, kf, V.cnt);
+            green = route_green(pk, e, V.phase[e >> 2]);
             const int nc = V.cnt[tl];
             lead = green && nc > 0;
             if constexpr (View::kImg) {  // per-lane last-vehicle arrays: always readable
@@ -281,45 +230,25 @@ __device__ __forceinline__ void substep(View &V, const Topo &T, const IdmK &P, i
                 vl = lt.y;
             }
         }
-        const bool nofront = free_road || (green && !lead);
-        const float gap = (len - x0) + (green ? (xl - P.length) : P.min_gap);
-        const float acc = idm_sel(v0, gap, v0 - (lead ? vl : 0.0f), nofront, P);
-        float vn = clamp_speed(v0 + acc, P);
-        float xn = x0 + vn;
-        const bool over = xn > len;
-        V.req[l] = free_road ? kArrive : (over && green ? tl : -1);
-        const bool stop = !free_road && over && !green;
-        V.fx[l] = stop ? len : xn;
-        V.fv[l] = stop ? 0.0f : vn;
+        const FrontMove fm = front_move(f0.x, f0.y, len, free_road, green, lead, xl, vl, tl, P);
+        V.req[l] = fm.req;
+        V.fx[l] = fm.x;
+        V.fv[l] = fm.v;
     }
     __syncthreads();
     SIM_PROF(1);
 
-    // ---- B: target lanes grant one request
-    // All 5 request slots are read at once; the first requester in the order
-    // rotated by t % 5 is the only one considered (granted if there is room).
+    // ---- B: target lanes grant one request (all 5 request slots read at once)
     for (int tl = tid; tl < NL; tl += nt) {
         int as, o;
         if (!feed_src(T, tl / 3, as, o)) continue;
-        int f[5];
-        uint32_t mask = 0;
-#pragma unroll
-        for (int i = 0; i < 5; i++) {
-            f[i] = feeder(as, o, i);
-            mask |= (V.req[f[i]] == tl ? 1u : 0u) << i;
-        }
+        const int f0 = feeder(as, o, 0), f1 = feeder(as, o, 1), f2 = feeder(as, o, 2),
+                  f3 = feeder(as, o, 3), f4 = feeder(as, o, 4);
+        const uint32_t mask = request_mask(V.req, tl, f0, f1, f2, f3, f4);
         if (!mask) continue;
-        const int start = t % 5;
-        const uint32_t rot = ((mask >> start) | (mask << (5 - start))) & 31u;
-        int k = start + __ffs(rot) - 1;
-        if (k >= 5) k -= 5;
-        int fsel = f[0];
-#pragma unroll
-        for (int i = 1; i < 5; i++) fsel = k == i ? f[i] : fsel;
-        int nc = V.cnt[tl];
-        bool room = nc < cap;
-        if (room && nc > 0) room = (V.last(tl, nc).x - P.length) >= P.min_gap;
-        if (room) V.gfrom[tl] = fsel;
+        const int nc = V.cnt[tl];
+        if (has_room(nc, cap, nc > 0 ? V.last(tl, nc).x : 0.0f, P))
+            V.gfrom[tl] = grant_pick(mask, f0, f1, f2, f3, f4, t);
     }
     __syncthreads();
     SIM_PROF(2);
@@ -348,48 +277,28 @@ __device__ __forceinline__ void substep(View &V, const Topo &T, const IdmK &P, i
         float lead_x_new = V.fx[l];
         float fvn = V.fv[l];
         const int rq = V.req[l];
-        bool pop = false;
-        if (rq == kArrive) {
-            pop = lead_x_new >= len;
-            if (pop) atomicAdd(&V.stats[1], 1);
-        } else if (rq >= 0) {
-            // granted? the target lane recorded the source lane in gfrom
-            pop = V.gfrom[rq] == l;
-            if (!pop) {
-                lead_x_new = len;
-                fvn = 0.0f;
-            }
-        }
+        // granted? the target lane recorded the source lane in gfrom
+        const bool pop = front_outcome(rq, rq >= 0 && V.gfrom[rq] == l, len, lead_x_new, fvn);
+        if (pop && rq == kArrive) atomicAdd(&V.stats[1], 1);
         if constexpr (View::kImg) {
             if (!pop) V.xv[l * V.C1 + hd] = make_float2(lead_x_new, fvn);
             else V.pdst[l] = V.dst[l * V.C1 + hd];  // the leaving front's route word, for pass D
         } else {
             if (!pop) V.st(base + hd, make_float2(lead_x_new, fvn));
         }
-        // actuated mode: a vehicle's body over the detector point dp during
-        // the substep (old front < dp + length, new front >= dp)
-        const float dp = len - P.det_dist, dpl = dp + P.length;
-        bool det = lead_x_new >= dp && lead_x_old < dpl;
+        const Detector dz(len, P);  // (actuated mode)
+        bool det = dz.crossed(lead_x_new, lead_x_old);
         float2 lastv2 = make_float2(lead_x_new, fvn);
-        // one follower: IDM against the old leader state, no overlap with the
-        // leader's new position
-        // (selects, no branches: the LDS walk below runs it for every lane of
-        // the wave up to the wave's longest lane, `act` false past a lane's end)
+        // one follower, which becomes the next one's leader (the LDS walk
+        // below runs it for every lane of the wave up to the wave's longest
+        // lane, `act` false past a lane's end)
         auto follow = [&](float xi, float vi, bool act = true) -> float2 {
-            const float gap = (lead_x_old - P.length) - xi;
-            const float acc = idm_acc(vi, gap, vi - lead_v_old, P);
-            const float vc = clamp_speed(vi + acc, P);
-            const float xc = xi + vc;
-            const float lim = lead_x_new - P.length, dl = lim - xi;
-            const bool over = xc > lim, back = lim < xi;
-            const float xn = over ? (back ? xi : lim) : xc;
-            const float vn = over ? (back ? 0.0f : dl) : vc;
-            if (kAct) det = det || (act && xn >= dp && xi < dpl);
-            const float2 r = make_float2(xn, vn);
+            const float2 r = follow_rule(xi, vi, lead_x_old, lead_v_old, lead_x_new, P);
+            if (kAct) det = det || (act && dz.crossed(r.x, xi));
             lastv2 = act ? r : lastv2;
             lead_x_old = act ? xi : lead_x_old;
             lead_v_old = act ? vi : lead_v_old;
-            lead_x_new = act ? xn : lead_x_new;
+            lead_x_new = act ? r.x : lead_x_new;
             return r;
         };
         if constexpr (View::kImg) {
@@ -470,8 +379,6 @@ __device__ __forceinline__ void substep(View &V, const Topo &T, const IdmK &P, i
     for (int tl = tid; tl < NL; tl += nt) {
         const int f = V.gfrom[tl];
         if (f < 0) continue;
-        const int e2 = tl / 3;
-        (void)e2;
         const float over = V.fx[f] - lane_length(T, f / 3);
         const float vin = V.fv[f];
         // the source lane already popped its front; read its (old) destination
@@ -483,13 +390,8 @@ __device__ __forceinline__ void substep(View &V, const Topo &T, const IdmK &P, i
             const int fh = V.head[f] == 0 ? cap - 1 : V.head[f] - 1;
             dv = route_advance(V.dst[(size_t)f * cap + fh]);
         }
-        int nc = V.cnt[tl];
-        float xe = over;
-        if (nc > 0) {
-            float lim = V.last(tl, nc).x - P.length - P.min_gap;
-            if (lim < xe) xe = lim;
-        }
-        if (xe < 0.0f) xe = 0.0f;
+        const int nc = V.cnt[tl];
+        const float xe = entry_x(over, nc > 0, nc > 0 ? V.last(tl, nc).x : 0.0f, P);
         DMDQN_DBG(nc < cap, DBG_SIM_RING);  // pass B granted only with room
         if constexpr (View::kImg) {
             V.putp(tl, nc, make_float2(xe, vin));
@@ -517,17 +419,11 @@ __device__ __forceinline__ void substep(View &V, const Topo &T, const IdmK &P, i
         if (e >= 4 * A) continue;
         int p = V.qptr[e];
         if (p >= V.q_off[e + 1]) continue;
-        const int id = qn[q].id;
-        if ((long long)id * S.period_ms > (long long)t * 1000) continue;
+        if (!departed(qn[q].id, S.period_ms, t)) continue;
         const int d0 = qn[q].dst;
-        const int aj = e >> 2, d = e & 3, h = opp(d);
-        // a one-edge route departs on the straight lanes (its origin is its end)
-        const int m = on_final_edge(d0, e) ? (int)MV_S : movement(h, out_dir(T, aj, h, d0));
-        const int k = lane_for_move(m, e, V.cnt);
-        const int l = e * 3 + k;
+        const int l = insert_lane(T, e, d0, V.cnt);
         const int nc = V.cnt[l];
-        if (nc >= cap) continue;
-        if (nc > 0 && V.last(l, nc).x < 2.0f * P.length + P.min_gap) continue;
+        if (!insert_room(nc, cap, nc > 0 ? V.last(l, nc).x : 0.0f, P)) continue;
         if constexpr (View::kImg) {
             V.putp(l, nc, make_float2(P.length, 0.0f));
             V.set_dstp(l, nc, d0);
@@ -636,10 +532,6 @@ __device__ __forceinline__ void fused_act_done(const dmdqn_env_fuse &F, int A, b
 // of this thread's first two (agent, 4-byte group) store slots, and the
 // reward's pre-step sum of agent `tid` (train.py:159-165).
 constexpr int kPreWords = 2;
-#ifndef DMDQN_FUSE_PREFETCH
-#define DMDQN_FUSE_PREFETCH 1
-#endif
-constexpr bool kFusePre = DMDQN_FUSE_PREFETCH;  // LDS path (A/B switch)
 struct TailPre {
     uint32_t ws[kPreWords];
     double sum;
@@ -780,15 +672,6 @@ __host__ __device__ inline size_t sim_lds_bytes(int R, int C, int cap) {
            (size_t)A * 16 + 16 + (size_t)(4 * A + 1) * 4 + (size_t)A * 48;  // q_off, last_det
 }
 
-// Sum over the wave (integer: exact in any order); the block totals below take
-// one LDS atomic per wave instead of one per thread at a single address, which
-// the LDS serialises lane by lane (up to 1024-way in the 8x8 register path).
-__device__ __forceinline__ int wave_sum(int x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
 // One RL step per env (block).  kLDS: the env's state is staged into LDS for
 // the K substeps (every pass is then an LDS-latency loop instead of an L2 one:
 // pass C walks each lane's vehicles front to back); only occupied positions
@@ -802,7 +685,9 @@ __global__ void __launch_bounds__(256, 4) k_sim_step(dmdqn_sim S, dmdqn_idm Pa, 
                                                   dmdqn_env_fuse F) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     const int t0 = S.t_env ? S.t_env[blockIdx.x] : t0_arg;  // the replica's own clock
+#ifdef DMDQN_SIM_PROFILE
     const uint64_t prof_t0 = __builtin_amdgcn_s_memrealtime();
+#endif
     const IdmK P(Pa);
     // topology tables after the state image (kLDS) or alone (global path)
     const size_t topo_off = kLDS ? sim_lds_bytes(S.R, S.C, S.cap_lane) : 0;
@@ -823,7 +708,7 @@ __global__ void __launch_bounds__(256, 4) k_sim_step(dmdqn_sim S, dmdqn_idm Pa, 
     TailPre pre{};
     if constexpr (kFuse) {
         my_act = fused_act(F, A, reinterpret_cast<uint32_t *>(dyn + fl.mt_off), act_fast);
-        if constexpr (kFusePre) pre = fused_prefetch(F, A);
+        pre = fused_prefetch(F, A);
     }
     if constexpr (kLDS) {
         const int C1 = V.C1;
@@ -901,20 +786,11 @@ __global__ void __launch_bounds__(256, 4) k_sim_step(dmdqn_sim S, dmdqn_idm Pa, 
         if (tid < 4) V.stats[tid] = G.stats[tid];
     }
     if constexpr (kFuse) {
-        if (tid < A) {  // A <= blockDim (dmdqn_env_step)
-            V.phase[tid] = stride * my_act;
-            V.ts[tid] = t0;
-        }
+        // A <= blockDim (dmdqn_env_step)
+        if (tid < A) set_phase(my_act, stride, t0, V.phase[tid], V.ts[tid]);
     } else if (actions) {
-        for (int a = tid; a < A; a += nt) {
-            // a negative action: no setPhase, the junction's program runs on
-            // with its timer (the reference class's skipped actions)
-            const int act = actions[(size_t)blockIdx.x * A + a];
-            if (act >= 0) {
-                V.phase[a] = stride * act;
-                V.ts[a] = t0;
-            }
-        }
+        for (int a = tid; a < A; a += nt)
+            set_phase(actions[(size_t)blockIdx.x * A + a], stride, t0, V.phase[a], V.ts[a]);
     }
     __syncthreads();
     if constexpr (kFuse) fused_act_done(F, A, act_fast, my_act);
@@ -925,10 +801,12 @@ __global__ void __launch_bounds__(256, 4) k_sim_step(dmdqn_sim S, dmdqn_idm Pa, 
         qn[q] = QNext{0, 0};
         if (e < 4 * A && V.qptr[e] < V.q_off[e + 1]) qn[q] = next_vehicle(V, V.qptr[e]);
     }
+#ifdef DMDQN_SIM_PROFILE
     uint64_t prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_t = __builtin_amdgcn_s_memrealtime();
     prof[6] = prof_t - prof_t0;  // staging
-    RouteCache rc{-1, 0, 0, 0};
-    for (int k = 0; k < K; k++) substep<kAct>(V, T, P, t0 + k, qn, rc, prof, prof_t);
+#endif
+    RouteCache rc;
+    for (int k = 0; k < K; k++) substep<kAct>(V, T, P, t0 + k, qn, rc SIM_PROF_ARGS);
     const int t = t0 + K;
     // halting counts on the observed (incoming) lanes + bookkeeping
     __shared__ int s_running, s_pending;
@@ -971,7 +849,7 @@ __global__ void __launch_bounds__(256, 4) k_sim_step(dmdqn_sim S, dmdqn_idm Pa, 
         G.stats[1] = V.stats[1];
         G.stats[2] = s_running;
         G.stats[3] = s_pending;
-        done[blockIdx.x] = (t >= max_time || (s_running + s_pending) == 0) ? 1 : 0;
+        done[blockIdx.x] = episode_done(t, max_time, s_running, s_pending) ? 1 : 0;
         if (S.t_env) S.t_env[blockIdx.x] = t;
     }
     if constexpr (kLDS) {
@@ -999,8 +877,8 @@ __global__ void __launch_bounds__(256, 4) k_sim_step(dmdqn_sim S, dmdqn_idm Pa, 
     }
     if constexpr (kFuse) {
         __syncthreads();  // the write-back has read the image: its slots are scratch now
-        const bool done_e = t >= max_time || (s_running + s_pending) == 0;
-        fused_tail<kFusePre>(F, S.R, S.C, t, done_e, my_act, pre, s_halt, V.phase, V.ts,
+        const bool done_e = episode_done(t, max_time, s_running, s_pending);
+        fused_tail<true>(F, S.R, S.C, t, done_e, my_act, pre, s_halt, V.phase, V.ts,
                              dyn + fl.tail_off);
     }
 #ifdef DMDQN_SIM_PROFILE
@@ -1021,15 +899,9 @@ __global__ void __launch_bounds__(256, 4) k_sim_step(dmdqn_sim S, dmdqn_idm Pa, 
 // lane instead of the ring image's 240 (4x4: 11 KB instead of 65 KB), so every
 // env of a 1024-replica launch is resident at once (4 per CU; 8x8: one
 // 1024-thread block per CU), and pass C walks registers instead of LDS.
-// Same passes, same IEEE operation order as the LDS path / oracle_sim.c
-// (bit-exact); the rings are written back compacted (head 0).
+// Same passes and the same rules (sim_rules.hpp) as the LDS path, bit-exact
+// against oracle_sim.c; the rings are written back compacted (head 0).
 constexpr int RCAP = 24;
-
-__device__ __forceinline__ int wave_max_uniform(int x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = max(x, __shfl_xor(x, off));
-    return __builtin_amdgcn_readfirstlane(x);
-}
 
 // A lane's vehicle speeds.  In registers for blocks of up to 512 threads.
 // A 1024-thread block (8x8: 128 VGPRs per thread) cannot hold three RCAP
@@ -1218,22 +1090,20 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
         head0 = G.head[tid];
     }
     // ---- LDS: published per-lane values, signals, detector times, stats, topology
-    // lane arrays LS entries apart (sim_reg_lds_bytes)
-    constexpr int LS_ = SIM_LANE_STRIDE_NT ? NT : 0;
-    const int LS = LS_ ? LS_ : NL;
+    // lane arrays NT entries apart (sim_reg_lds_bytes)
     int32_t *s_cnt = reinterpret_cast<int32_t *>(dyn);
-    float *s_lx = reinterpret_cast<float *>(s_cnt + LS), *s_lv = s_lx + LS;
-    int32_t *s_req = reinterpret_cast<int32_t *>(s_lv + LS), *s_gfrom = s_req + LS;
-    float *s_fx = reinterpret_cast<float *>(s_gfrom + LS), *s_fv = s_fx + LS;
-    int32_t *s_mdst = reinterpret_cast<int32_t *>(s_fv + LS), *s_ins = s_mdst + LS;
-    int32_t *s_phase = s_ins + LS, *s_ts = s_phase + A, *s_ldet = s_ts + A;
+    float *s_lx = reinterpret_cast<float *>(s_cnt + NT), *s_lv = s_lx + NT;
+    int32_t *s_req = reinterpret_cast<int32_t *>(s_lv + NT), *s_gfrom = s_req + NT;
+    float *s_fx = reinterpret_cast<float *>(s_gfrom + NT), *s_fv = s_fx + NT;
+    int32_t *s_mdst = reinterpret_cast<int32_t *>(s_fv + NT), *s_ins = s_mdst + NT;
+    int32_t *s_phase = s_ins + NT, *s_ts = s_phase + A, *s_ldet = s_ts + A;
     int32_t *s_stats = s_ldet + 12 * A;  // inserted, arrived, running, pending
     // fused step: the MT stream past the block's own LDS; the halting counts
     // later in the topology tables' place, the epilogue's scratch in the
     // published-lane arrays (both dead by then).  The actions are drawn
     // first: their two dependent loads (the stream position, then its words)
     // overlap the topology's and the lanes' loads below.
-    const FuseLayout fl = fuse_layout(sim_reg_lds_bytes(S.R, S.C, LS), 0, (size_t)LS * 9 * 4, A);
+    const FuseLayout fl = fuse_layout(sim_reg_lds_bytes(S.R, S.C, NT), 0, (size_t)NT * 9 * 4, A);
     int32_t *const s_halt = s_stats + 4;
     int my_act = 0;
     bool act_fast = false;
@@ -1247,7 +1117,7 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
     const uint64_t prof_topo = __builtin_amdgcn_s_memrealtime();  // after the act draw + topology
 #endif
     size_t perm_off = 0;
-    (void)reg_lds_total(S.R, S.C, kFuse, LS, NT, &perm_off);
+    (void)reg_lds_total(S.R, S.C, kFuse, NT, NT, &perm_off);
     uint16_t *const s_lane = reinterpret_cast<uint16_t *>(dyn + perm_off);
     lane_order<NT>(cnt0, head0, NL, s_lane, reinterpret_cast<int32_t *>(dyn + perm_off + (size_t)NT * 2),
                    s_cnt, s_gfrom);  // (s_gfrom: the heads until pass B)
@@ -1263,7 +1133,7 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
     constexpr bool kL = NT > 512;  // speeds in the LDS column (VColL)
     float X_[RCAP], V_[RCAP];
     VColL Vc{nullptr, 0, NT};
-    if constexpr (kL) Vc.p = reinterpret_cast<float *>(dyn + reg_vcol_off(S.R, S.C, kFuse, LS)) + tid;
+    if constexpr (kL) Vc.p = reinterpret_cast<float *>(dyn + reg_vcol_off(S.R, S.C, kFuse, NT)) + tid;
     uint32_t D2_[RCAP2];
     int n = 0;
     float lx = 0.0f, lv = 0.0f;
@@ -1333,15 +1203,14 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
     if constexpr (kFuse) {
         // (1024-thread blocks have no VGPRs to hold the prefetch across the substeps)
         if constexpr (!kL) pre = fused_prefetch(F, A);
-        if (tid < A) {  // A <= NT (dmdqn_env_step)
-            s_phase[tid] = stride * my_act;
-            s_ts[tid] = t0;
-        }
+        // A <= NT (dmdqn_env_step)
+        if (tid < A) set_phase(my_act, stride, t0, s_phase[tid], s_ts[tid]);
     } else {
         for (int a = tid; a < A; a += NT) {
-            const int act = actions ? actions[(size_t)blockIdx.x * A + a] : -1;  // < 0: keep
-            s_phase[a] = act >= 0 ? stride * act : G.phase[a];
-            s_ts[a] = act >= 0 ? t0 : G.ts[a];
+            int32_t p = G.phase[a], ts = G.ts[a];
+            set_phase(actions ? actions[(size_t)blockIdx.x * A + a] : -1, stride, t0, p, ts);
+            s_phase[a] = p;
+            s_ts[a] = ts;
         }
     }
     if (S.actuated)
@@ -1361,24 +1230,8 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
 
     // TL at time t: natural phase advance (and the actuated gap-out of phase 0)
     auto tl_pass = [&](int t) {
-        for (int a = tid; a < A; a += NT) {
-            const int p = s_phase[a], el = t - s_ts[a];
-            bool sw;
-            if (S.actuated && p == 0) {
-                constexpr uint32_t gl = green_lanes(0x11BB);  // green_mask(0)
-                int last = kNoDetection;
-#pragma unroll
-                for (int k = 0; k < 12; k++)
-                    if ((gl >> k) & 1u) last = max(last, s_ldet[a * 12 + k]);
-                sw = el >= kActMax || (el >= kActMin && (float)(t - last) > P.max_gap);
-            } else {
-                sw = el >= phase_dur(p);
-            }
-            if (sw) {
-                s_phase[a] = (p + 1) % 12;
-                s_ts[a] = t;
-            }
-        }
+        for (int a = tid; a < A; a += NT)
+            tl_advance(s_phase[a], s_ts[a], t, S.actuated, s_ldet + a * 12, P);
     };
     // an insertion the lane's origin queue ordered in the previous pass E
 #define TAKE_INSERT()                                                   \
@@ -1395,7 +1248,7 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
 
     tl_pass(t0);
     __syncthreads();
-    int rc_d0 = -1, rc_pk = 0;  // pass A's route cache (route words are >= 0)
+    RouteCache rc;  // pass A's route decision of this lane's front
     // Pass B's five feeder lanes of this thread's lane (static: computed once
     // here, 10 bits each, bit 20 of fd_pk1 = the lane has feeders) instead of
     // per substep
@@ -1421,63 +1274,29 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
         const int l = tq < NL ? (int)s_lane[tq] : tq, e = l / 3, kf = l - 3 * (l / 3);
         const float len = LANE_LEN();
         TAKE_INSERT();
-        // ---- A: the front vehicle decides (route, target lane, IDM, request).
-        // One IDM evaluation, its inputs chosen by selects (free road: no
-        // interaction term; green with a vehicle on the target lane: that
-        // vehicle; red / yellow: the stop line), as the LDS path's pass A --
-        // separate evaluations per branch ran every one a divergent wave
-        // took.  The route decisions of the front (its out-direction,
-        // movement, next edge and the movement it will take there) depend
-        // only on the lane and the front's route word: cached per thread
-        // (rc_d0; packed e2 | m << 12 | (mv2 + 1) << 16) and recomputed when
-        // the front changes.
-        int rq = -1;
-        float fx = 0.0f, fv = 0.0f;
+        // ---- A: the front vehicle decides (route_decide, kept in rc across
+        // substeps until the front changes; front_move: one IDM evaluation --
+        // separate ones per branch ran every one a divergent wave took)
+        FrontMove fm{0.0f, 0.0f, -1};
         if (own && n > 0) {
-            const float x0 = X_[0], v0 = vget<kL>(V_, Vc, 0);
             const int d0 = dget(D2_, 0);
-            const bool free_road = e >= 4 * A || on_final_edge(d0, e);
+            const bool free_road = on_free_road(T, e, d0);
             bool green = false, lead = false;
             int tl = -1;
             float xl = 0.0f, vl = 0.0f;
             if (!free_road) {
-                const int aj = e >> 2, d = e & 3, h = opp(d);
-                if (rc_d0 != d0) {
-                    const int o = out_dir(T, aj, h, d0);
-                    const int m = movement(h, o);
-                    DMDQN_DBG(T.nbr(aj, o) >= 0 || T.exit_id[aj * 4 + o] >= 0, DBG_SIM_EDGE);
-                    const int e2 = next_edge(T, aj, o);
-                    const int w2 = route_advance(d0);
-                    int mv2 = -1;
-                    if (!(e2 >= 4 * A || on_final_edge(w2, e2))) {
-                        const int h2 = opp(e2 & 3);
-                        mv2 = movement(h2, out_dir(T, e2 >> 2, h2, w2));
-                    }
-                    rc_pk = e2 | (m << 12) | ((mv2 + 1) << 16);
-                    rc_d0 = d0;
-                }
-                const int e2 = rc_pk & 0xfff, m = (rc_pk >> 12) & 0xf, mv2 = (rc_pk >> 16) - 1;
-                const int k2 = mv2 < 0 ? kf : lane_for_move(mv2, e2, s_cnt);
-                tl = e2 * 3 + k2;
-                green = (green_mask(s_phase[aj]) >> (d * 4 + m)) & 1;
+                if (rc.d0 != d0) rc = RouteCache{d0, route_decide(T, e, d0)};
+                tl = route_target(rc.pk, kf, s_cnt);
+                green = route_green(rc.pk, e, s_phase[e >> 2]);
                 lead = green && s_cnt[tl] > 0;
                 xl = s_lx[tl];
                 vl = s_lv[tl];
             }
-            const bool nofront = free_road || (green && !lead);
-            const float gap = (len - x0) + (green ? (xl - P.length) : P.min_gap);
-            const float acc = idm_sel(v0, gap, v0 - (lead ? vl : 0.0f), nofront, P);
-            fv = clamp_speed(v0 + acc, P);
-            fx = x0 + fv;
-            const bool over = fx > len;
-            rq = free_road ? kArrive : (over && green ? tl : -1);
-            const bool stop = !free_road && over && !green;
-            fx = stop ? len : fx;
-            fv = stop ? 0.0f : fv;
-            s_fx[l] = fx;
-            s_fv[l] = fv;
+            fm = front_move(X_[0], vget<kL>(V_, Vc, 0), len, free_road, green, lead, xl, vl, tl, P);
+            s_fx[l] = fm.x;
+            s_fv[l] = fm.v;
         }
-        if (own) s_req[l] = rq;
+        if (own) s_req[l] = fm.req;
         __syncthreads();
         SIM_PROF(1);
 
@@ -1485,27 +1304,10 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
         if (own) {
             int g = -1;
             if (fd_pk1 >> 20) {  // the lane has feeders (fd_pk0 / fd_pk1, above the loop)
-                int f[5];
-                f[0] = fd_pk0 & 1023;
-                f[1] = (fd_pk0 >> 10) & 1023;
-                f[2] = (fd_pk0 >> 20) & 1023;
-                f[3] = fd_pk1 & 1023;
-                f[4] = (fd_pk1 >> 10) & 1023;
-                uint32_t mask = 0;
-#pragma unroll
-                for (int i = 0; i < 5; i++) mask |= (s_req[f[i]] == l ? 1u : 0u) << i;
-                if (mask) {
-                    const int start = t % 5;
-                    const uint32_t rot = ((mask >> start) | (mask << (5 - start))) & 31u;
-                    int kk = start + __ffs(rot) - 1;
-                    if (kk >= 5) kk -= 5;
-                    int fsel = f[0];
-#pragma unroll
-                    for (int i = 1; i < 5; i++) fsel = kk == i ? f[i] : fsel;
-                    bool room = n < cap;
-                    if (room && n > 0) room = (lx - P.length) >= P.min_gap;
-                    if (room) g = fsel;
-                }
+                const int f0 = fd_pk0 & 1023, f1 = (fd_pk0 >> 10) & 1023, f2 = (fd_pk0 >> 20) & 1023,
+                          f3 = fd_pk1 & 1023, f4 = (fd_pk1 >> 10) & 1023;
+                const uint32_t mask = request_mask(s_req, l, f0, f1, f2, f3, f4);
+                if (mask && has_room(n, cap, lx, P)) g = grant_pick(mask, f0, f1, f2, f3, f4, t);
             }
             s_gfrom[l] = g;
         }
@@ -1517,26 +1319,18 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
             const int nm = wave_max_uniform(own ? n : 0);
             if (own && n > 0) {
                 const float lead_x_old0 = X_[0], lead_v_old0 = vget<kL>(V_, Vc, 0);
-                float lead_x_new = fx, fvn = fv;
-                bool pop = false;
-                if (rq == kArrive) {
-                    pop = lead_x_new >= len;
-                    if (pop) atomicAdd(&s_stats[1], 1);
-                } else if (rq >= 0) {
-                    pop = s_gfrom[rq] == l;
-                    if (!pop) {
-                        lead_x_new = len;
-                        fvn = 0.0f;
-                    } else {
-                        s_mdst[l] = route_advance(dget(D2_, 0));
-                    }
-                }
-                if (!pop) {
+                const int rq = fm.req;
+                float lead_x_new = fm.x, fvn = fm.v;
+                const bool pop = front_outcome(rq, rq >= 0 && s_gfrom[rq] == l, len, lead_x_new, fvn);
+                if (pop) {  // arrived, or left for its target lane (pass D reads its route word)
+                    if (rq == kArrive) atomicAdd(&s_stats[1], 1);
+                    else s_mdst[l] = route_advance(dget(D2_, 0));
+                } else {
                     X_[0] = lead_x_new;
                     vset<kL>(V_, Vc, 0, fvn);
                 }
-                const float dp = len - P.det_dist, dpl = dp + P.length;
-                bool det = lead_x_new >= dp && lead_x_old0 < dpl;
+                const Detector dz(len, P);  // (actuated mode)
+                bool det = dz.crossed(lead_x_new, lead_x_old0);
                 float lead_x_old = lead_x_old0, lead_v_old = lead_v_old0;
                 float last_x = X_[0], last_v = vget<kL>(V_, Vc, 0);
                 // (LDS speeds: vehicle i + 1's speed is read while vehicle i is
@@ -1563,26 +1357,16 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
                         } else {
                             vi = V_[i];
                         }
-                        const float gap = (lead_x_old - P.length) - xi;
-                        const float acc = idm_acc(vi, gap, vi - lead_v_old, P);
-                        float vn = clamp_speed(vi + acc, P);
-                        float xn = xi + vn;
-                        const float lim = lead_x_new - P.length;
-                        // no overlap with the leader's new position: stop at
-                        // lim, or stand if lim is behind (selects, not branches)
-                        const bool over = xn > lim, stand = lim < xi;
-                        const float xc = stand ? xi : lim, vc = stand ? 0.0f : lim - xi;
-                        xn = over ? xc : xn;
-                        vn = over ? vc : vn;
-                        X_[i] = xn;
-                        if constexpr (kL) *pc = vn;
-                        else V_[i] = vn;
-                        det = det || (xn >= dp && xi < dpl);
+                        const float2 r = follow_rule(xi, vi, lead_x_old, lead_v_old, lead_x_new, P);
+                        X_[i] = r.x;
+                        if constexpr (kL) *pc = r.y;
+                        else V_[i] = r.y;
+                        det = det || dz.crossed(r.x, xi);
                         lead_x_old = xi;
                         lead_v_old = vi;
-                        lead_x_new = xn;
-                        last_x = xn;
-                        last_v = vn;
+                        lead_x_new = r.x;
+                        last_x = r.x;
+                        last_v = r.y;
                     }
                 }
                 if (pop) {
@@ -1610,12 +1394,7 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
                 const float over = s_fx[f] - lane_length(T, f / 3);
                 const float vin = s_fv[f];
                 const int dv = s_mdst[f];
-                float xe = over;
-                if (n > 0) {
-                    const float lim = lx - P.length - P.min_gap;
-                    if (lim < xe) xe = lim;
-                }
-                if (xe < 0.0f) xe = 0.0f;
+                const float xe = entry_x(over, n > 0, lx, P);
                 DMDQN_DBG(n < cap && n < RCAP, DBG_SIM_RING);  // pass B granted only with room
                 lane_append<kL>(X_, V_, Vc, D2_, n, lx, lv, xe, vin, dv);
                 s_cnt[l] = n;
@@ -1629,16 +1408,11 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
         // ---- E: each origin queue inserts its next departed vehicle if there is
         // room (the lane's owner takes it into its registers at the next pass);
         // then the signals advance to t + 1
-        if (leader && qp < qend && (long long)qid * S.period_ms <= (long long)t * 1000) {
-            const int q = tid, d0 = qdst;
-            const int aj = q >> 2, h = opp(q & 3);
-            // a one-edge route departs on the straight lanes (its origin is its end)
-            const int m = on_final_edge(d0, q) ? (int)MV_S : movement(h, out_dir(T, aj, h, d0));
-            const int li = q * 3 + lane_for_move(m, q, s_cnt);
+        if (leader && qp < qend && departed(qid, S.period_ms, t)) {
+            const int d0 = qdst;
+            const int li = insert_lane(T, tid, d0, s_cnt);
             const int nc = s_cnt[li];
-            bool room = nc < cap;
-            if (room && nc > 0) room = s_lx[li] >= 2.0f * P.length + P.min_gap;
-            if (room) {
+            if (insert_room(nc, cap, s_lx[li], P)) {
                 s_cnt[li] = nc + 1;
                 s_lx[li] = P.length;
                 s_lv[li] = 0.0f;
@@ -1718,11 +1492,11 @@ k_sim_step_reg(dmdqn_sim S, dmdqn_idm Pa, const int32_t *actions, int stride, in
         G.stats[1] = s_stats[1];
         G.stats[2] = s_stats[2];
         G.stats[3] = s_stats[3];
-        done[blockIdx.x] = (t >= max_time || (s_stats[2] + s_stats[3]) == 0) ? 1 : 0;
+        done[blockIdx.x] = episode_done(t, max_time, s_stats[2], s_stats[3]) ? 1 : 0;
         if (S.t_env) S.t_env[blockIdx.x] = t;
     }
     if constexpr (kFuse) {
-        const bool done_e = t >= max_time || (s_stats[2] + s_stats[3]) == 0;
+        const bool done_e = episode_done(t, max_time, s_stats[2], s_stats[3]);
         const int act_back = tid < A ? reinterpret_cast<const int32_t *>(dyn + fl.mt_off)[tid] : 0;
         fused_tail<!kL>(F, S.R, S.C, t, done_e, act_back, pre, s_halt, s_phase, s_ts,
                         dyn + fl.tail_off);
@@ -1821,8 +1595,8 @@ static int launch_sim(const dmdqn_sim *sim, const dmdqn_idm *idm, const int32_t 
     const dmdqn_env_fuse f = F ? *F : dmdqn_env_fuse{};
     if (use_reg) {
         const int nt = NL <= 256 ? 256 : NL <= 512 ? 512 : 1024;
-        const int ls = SIM_LANE_STRIDE_NT ? nt : NL;  // the kernel's lane-array stride
-        const size_t rlds = reg_lds_total(sim->R, sim->C, F != nullptr, ls, nt, nullptr);
+        // (the kernel's lane arrays are nt entries apart)
+        const size_t rlds = reg_lds_total(sim->R, sim->C, F != nullptr, nt, nt, nullptr);
         DMDQN_REQUIRE(rlds <= 160 * 1024, "dmdqn_sim_step: register path needs %zu bytes of LDS", rlds);
         auto go = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(sim->E), dim3(nt), rlds, as_stream(stream), *sim, *idm,

@@ -1,4 +1,5 @@
-// sim.hpp -- grid geometry, routing, signal program and IDM for sim.hip.
+// sim.hpp -- grid geometry, routing tables, signal program and IDM: what the
+// simulation rules (sim_rules.hpp) and their storage forms (sim.hip) build on.
 #pragma once
 #include "common.hpp"
 
@@ -207,16 +208,6 @@ __device__ __forceinline__ int lane_for_move(int m, int e, const int32_t *cnt) {
     return cnt[e * 3 + 1] <= cnt[e * 3 + 0] ? 1 : 0;
 }
 
-// Lane a vehicle takes when entering edge e2 from lane index kf; w2 is its
-// route word on e2 (route_advance of the word it has now).
-__device__ __forceinline__ int lane_for(const Topo &T, int e2, int kf, int w2,
-                                        const int32_t *cnt) {
-    if (e2 >= 4 * T.A || on_final_edge(w2, e2)) return kf;  // connections keep the lane index
-    int h2 = opp(e2 & 3);
-    int o2 = out_dir(T, e2 >> 2, h2, w2);
-    return lane_for_move(movement(h2, o2), e2, cnt);
-}
-
 // Upstream junction `as` and out-direction `o` of the movements that feed edge
 // e2; false for fringe-in edges (nothing upstream).
 __device__ __forceinline__ bool feed_src(const Topo &T, int e2, int &as, int &o) {
@@ -281,14 +272,12 @@ __device__ __forceinline__ float idm_div(float a, float b) {
     return __builtin_fmaf(r2, y, q);
 }
 
-__device__ __forceinline__ float idm_free(float v, const IdmK &P) {
-    float r = v * P.inv_vmax;
-    float r2 = r * r;
-    float r4 = r2 * r2;
-    return P.accel * (1.0f - r4);
-}
-
-__device__ __forceinline__ float idm_acc(float v, float s, float dv, const IdmK &P) {
+// The IDM acceleration, or (nofront) its free-road form, from one evaluation:
+// free road is the same expression without the interaction term, accel *
+// ((1 - r^4) - 0) == accel * (1 - r^4) exactly; red is idm_acc(v, s, v) = dv
+// of v - 0.
+__device__ __forceinline__ float idm_sel(float v, float s, float dv, bool nofront,
+                                         const IdmK &P) {
     float r = v * P.inv_vmax;
     float r2 = r * r;
     float r4 = r2 * r2;
@@ -298,24 +287,11 @@ __device__ __forceinline__ float idm_acc(float v, float s, float dv, const IdmK 
     s = __builtin_fmaxf(s, 0.01f);
     float q = idm_div(sstar, s);
     float t1 = 1.0f - r4;
-    return P.accel * (t1 - q * q);
+    return P.accel * (t1 - (nofront ? 0.0f : q * q));
 }
 
-// idm_acc, or idm_free when nofront, from one evaluation: free road is the
-// same expression without the interaction term, accel * ((1 - r^4) - 0) ==
-// accel * (1 - r^4) exactly; red is idm_acc(v, s, v) = dv of v - 0.
-__device__ __forceinline__ float idm_sel(float v, float s, float dv, bool nofront,
-                                         const IdmK &P) {
-    float r = v * P.inv_vmax;
-    float r2 = r * r;
-    float r4 = r2 * r2;
-    float ss = v * P.tau + (v * dv) * P.inv_two_sqrt_ab;
-    ss = __builtin_fmaxf(ss, 0.0f);
-    float sstar = P.min_gap + ss;
-    s = __builtin_fmaxf(s, 0.01f);
-    float q = idm_div(sstar, s);
-    float t1 = 1.0f - r4;
-    return P.accel * (t1 - (nofront ? 0.0f : q * q));
+__device__ __forceinline__ float idm_acc(float v, float s, float dv, const IdmK &P) {
+    return idm_sel(v, s, dv, false, P);
 }
 
 // v < 0 -> 0, v > vmax -> vmax, else v (oracle_sim.c's compares) as one

@@ -81,6 +81,14 @@ def test_fused_step_4x4_and_8x8_default_paths():
         _compare(ref, fus, _run(ref, 45), _run(fus, 45))
 
 
+def test_fused_step_5x5_default_path():
+    """5x5 (360 lanes; its LDS image does not fit two per CU) takes the
+    register path's 512-thread kernel, fused: the one instantiation the other
+    grids here do not reach."""
+    ref, fus = _trainer(False, 5, 5), _trainer(True, 5, 5)
+    _compare(ref, fus, _run(ref, 140), _run(fus, 140))
+
+
 @pytest.mark.parametrize("kind", ["actuated", "greedy", "shared", "sample_schedule"])
 def test_fused_step_variants(kind):
     kw = {}

@@ -100,6 +100,19 @@ def test_sim_8x8_matches_oracle():
     _run(8, 8, E=3, steps=40, check_every=5, full_state_at=(20,))
 
 
+@pytest.mark.parametrize("grid,actuated", [((5, 5), True), ((6, 6), False)])
+def test_sim_512_thread_register_path_matches_oracle(grid, actuated, lib_option):
+    """5x5 (360 lanes) and 6x6 (504, the most under 512) run the register
+    path's 512-thread kernel, which no other grid of the suite reaches.  It is
+    also launch_sim's default for them (their LDS images do not fit two per
+    CU); forced here so that the test does not depend on that rule.  Lanes
+    reach 14-15 vehicles: past the 12-position image, under the register
+    lanes' 24."""
+    lib_option("sim_path", "reg")
+    env = _run(*grid, E=3, steps=40, check_every=5, full_state_at=(20,), actuated=actuated)
+    assert 12 < env.max_cnt_seen <= 24, env.max_cnt_seen
+
+
 def test_sim_intended_mode_full_episode_and_reset():
     env = _run(2, 2, E=4, steps=240, mode="intended", check_every=20)
     assert env.t == 2400
