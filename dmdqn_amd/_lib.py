@@ -86,9 +86,10 @@ def _apply(lib, sigs):
 
 
 def tree_digest(root=None):
-    """The digest of the sources in this tree (build.tree_digest)."""
+    """The digest of the sources in this tree and of the compile flags of the
+    variant this process loads (build.tree_digest)."""
     from .build import tree_digest as td
-    return td(root)
+    return td(root, VARIANT)
 
 
 def verify_digest(lib, what, root=None, symbol="dmdqn_source_digest"):

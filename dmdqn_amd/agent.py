@@ -94,6 +94,8 @@ _lib.register({
     "dmdqn_learn_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p],
     "dmdqn_learn_grad_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_void_p],
     "dmdqn_adam_agents_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_void_p],
+    "dmdqn_learn_pair": [C.POINTER(CLearn), C.POINTER(CLearn), C.POINTER(CHParams),
+                         C.POINTER(CHParams), C.c_void_p],
     "dmdqn_target_soft_update_hp": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
 })
@@ -526,6 +528,19 @@ class AgentConfig:
         return cls(**known)
 
 
+class LearnToken:
+    """What learn_begin() fixes of one learn, so that its launch may follow
+    later (the trainer's paired learns, learn_pair_range): the index and loss /
+    metrics buffers of the agent's rotations, the ring window, the Keras Adam
+    constants and factors of this learn's step count, and whether it -- or the
+    learn after it -- is a hard target sync."""
+    __slots__ = ("idx", "loss", "qstats", "adam", "factors", "sync", "next_sync", "start", "n")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
 def _soft_after_shared(agent, sync):
     """The shared net's soft target update: one more launch on the one net
     after its Adam step (every rank holds the same net and takes the same
@@ -688,6 +703,8 @@ class BatchedDQN:
         self.learn_step_counter = 0
         self.epsilon = cfg.epsilon_start
         self.learn_launches = 0
+        self.pair_launches = 0  # learn_pair_range launches (two of the learns begun each)
+        self._last_tok = None
         self.learn_hook = None  # optional callable(before: bool), e.g. HIP event timing
         self.stamps = None      # optional int64 [NA, 16] device tensor: phase timestamps
         self.rn_out = None      # optional f32 [NA, batch] device tensor: the z-scored rewards
@@ -846,7 +863,9 @@ class BatchedDQN:
     def learn_begin(self, collect_stats=False):
         """The host half of learn(): the replay draws (or the presampled ones),
         the learn counter and the Keras Adam constants of this learn.  False
-        while underfilled.  The launches follow with learn_range(lo, hi) over
+        while underfilled, else the learn's LearnToken (true; it also fixes the
+        ring window, for a launch that follows later: learn_pair_range, or
+        learn_range(lo, hi, tok)).  The launches follow with learn_range(lo, hi) over
         agent ranges that cover [0, NA) -- independent agents, so ranges may
         run on different streams (trainer overlap "env" with side_learn)."""
         n = len(self.ring)
@@ -878,13 +897,20 @@ class BatchedDQN:
             self.qstats = qstats = self._qstats_bufs[k]
         self._last_learn = (alpha, c1, c2, eps, sync, qstats)
         self.learn_launches += 1
-        return True
+        nxt = self.learn_step_counter + 1
+        self._last_tok = LearnToken(
+            idx=self.idx, loss=self.loss, qstats=qstats, adam=(alpha, c1, c2, eps),
+            factors=self._last_factors, sync=sync, start=self.ring.start, n=self.learn_step_counter,
+            next_sync=cfg.target_update_frequency > 0 and nxt % cfg.target_update_frequency == 0)
+        return self._last_tok
 
-    def learn_range(self, lo, hi):
-        """Launch the learn begun by learn_begin() for agents [lo, hi) on the
-        current stream (the whole range for the shared net).  The timing hook
-        brackets the range that starts at agent 0.  Returns self.loss."""
-        alpha, c1, c2, eps, sync, qstats = self._last_learn
+    def learn_range(self, lo, hi, tok=None):
+        """Launch the learn begun by learn_begin() -- the last one, or the one
+        whose token is given -- for agents [lo, hi) on the current stream (the
+        whole range for the shared net).  The timing hook brackets the range
+        that starts at agent 0.  Returns the learn's loss buffer."""
+        tok = tok or self._last_tok
+        (alpha, c1, c2, eps), sync, qstats = tok.adam, tok.sync, tok.qstats
         cfg, ring = self.cfg, self.ring
         tau_f, omt_f = soft_update_consts(cfg.tau)
         hook = self.learn_hook if lo == 0 else None
@@ -905,20 +931,20 @@ class BatchedDQN:
                     shape = (self.NA, cfg.batch_size, K.ROW_FLOATS)
                     self._xs = torch.empty(shape, dtype=torch.float32, device=self.device)
                     self._xn = torch.empty(shape, dtype=torch.float32, device=self.device)
-                ring.gather_f32(self.idx, self._xs, self._xn)
+                ring.gather_f32(tok.idx, self._xs, self._xn)
                 xs, xn = self._xs, self._xn
 
             def sl(t):
                 return None if t is None else t[lo:hi]
             args = (sl(ring.s), sl(ring.n), sl(ring.a), sl(ring.d), sl(ring.r),
-                    sl(self.idx), sl(self.params), sl(self.adam_m), sl(self.adam_v),
-                    sl(self.target), sl(self.target_h), sl(self.loss), ring.start,
+                    sl(tok.idx), sl(self.params), sl(self.adam_m), sl(self.adam_v),
+                    sl(self.target), sl(self.target_h), sl(tok.loss), tok.start,
                     self.H, PRECISIONS[cfg.precision], sync, self.gamma_n, alpha, c1, c2,
                     eps, LOSSES[cfg.loss], sl(qstats), sl(self.rn_out), sl(self.stamps))
             kw = dict(grad=sl(self._split_grad), xs=xs, xn=xn, tau=float(tau_f),
                       one_minus_tau=float(omt_f))
             if self.swept:  # the range's slice of the per-agent arrays, like every tensor
-                s, d = self._last_factors
+                s, d = tok.factors
                 self._ops.learn_step_hp(*args, **kw, lr=sl(self.hp_lr), gamma_a=sl(self.hp_gamma),
                                         tau_a=sl(self.hp_tau), one_minus_tau_a=sl(self.hp_omt),
                                         adam_s=s, adam_d=d)
@@ -926,7 +952,46 @@ class BatchedDQN:
                 self._ops.learn_step(*args, **kw)
         if hook:
             hook(False)
-        return self.loss
+        return tok.loss
+
+    def learn_pair_range(self, tok0, tok1, lo, hi):
+        """Launch two consecutive learns -- tok0's, then tok1's, the tokens of
+        two learn_begin() calls in a row -- for agents [lo, hi) as ONE launch on
+        the current stream (dmdqn_learn_pair: each agent's second learn reads
+        its weights, Adam slots and target while the first one's writes are
+        still on the chip).  Bit-identical to learn_range(lo, hi, tok0) followed
+        by learn_range(lo, hi, tok1).  16-bit independent nets on int8 rows;
+        neither learn a hard target sync, neither with metrics' buffers missing
+        on one side.  Returns (tok0.loss, tok1.loss)."""
+        cfg, ring = self.cfg, self.ring
+        if self.shared or ring.row_format != "int8" or cfg.precision not in H16_DTYPES:
+            raise ValueError("learn_pair_range: 16-bit independent nets on int8 rows only")
+        if self._split_grad is not None:
+            raise ValueError("learn_pair_range: not with the split learn")
+        if tok0.sync or tok1.sync:
+            raise ValueError("learn_pair_range: a hard target sync runs as a single learn")
+        if tok1.n != tok0.n + 1 or tok0.idx is tok1.idx or tok0.loss is tok1.loss:
+            raise RuntimeError("learn_pair_range: not two consecutive learns with buffers of "
+                               "their own")
+        tau_f, omt_f = soft_update_consts(cfg.tau)
+        for t in (tok0, tok1):
+            if t.qstats is not None:
+                t.qstats[lo:hi].zero_()  # the kernels accumulate into it
+
+        def sl(t):
+            return None if t is None else t[lo:hi]
+        self._ops.learn_pair(
+            sl(ring.s), sl(ring.n), sl(ring.a), sl(ring.d), sl(ring.r), sl(self.params),
+            sl(self.adam_m), sl(self.adam_v), sl(self.target), sl(self.target_h), sl(tok0.idx),
+            sl(tok1.idx), sl(tok0.loss), sl(tok1.loss), tok0.start, tok1.start, self.H,
+            PRECISIONS[cfg.precision], self.gamma_n, list(tok0.adam), list(tok1.adam),
+            LOSSES[cfg.loss], qstats0=sl(tok0.qstats), qstats1=sl(tok1.qstats),
+            tau=float(tau_f), one_minus_tau=float(omt_f), lr=sl(self.hp_lr),
+            gamma_a=sl(self.hp_gamma), tau_a=sl(self.hp_tau), one_minus_tau_a=sl(self.hp_omt),
+            factors0=list(tok0.factors), factors1=list(tok1.factors))
+        if lo == 0:
+            self.pair_launches += 1
+        return tok0.loss, tok1.loss
 
     def c_learn_args(self):
         """The dmdqn_learn_args struct of the last learn (ctypes), for tests that

@@ -59,6 +59,11 @@ PER_FILE = {
     "learn.hip": ["-ffp-contract=fast"],
     "learn_f16.hip": ["-ffp-contract=fast"],
     "learn_bf16.hip": ["-ffp-contract=fast"],
+    # the paired learn: the arithmetic flags of the single learn; without the
+    # backend's loop-invariant code motion, which hoists the body's lane-derived
+    # addresses out of the two rounds and spills them (learn_h16.hpp, at the kernel)
+    "learn_f16_x2.hip": ["-ffp-contract=fast", "-mllvm", "-disable-machine-licm"],
+    "learn_bf16_x2.hip": ["-ffp-contract=fast", "-mllvm", "-disable-machine-licm"],
 }
 DEFAULT_FP = ["-ffp-contract=off"]
 # experiment hook: extra flags for every file (e.g. -D switches while tuning)
@@ -69,7 +74,8 @@ EXTRA = os.environ.get("DMDQN_EXTRA_FLAGS", "").split()
 # records their digest; bench.py flags a figure measured on other sources as
 # stale): the learn kernels, and the env step (sim + fused observe / store).
 KERNEL_SOURCES = {
-    "learn": ["learn.hip", "learn_f16.hip", "learn_bf16.hip", "learn_h16.hpp", "learn_shared.hip",
+    "learn": ["learn.hip", "learn_f16.hip", "learn_bf16.hip", "learn_h16.hpp", "learn_h16_body.hpp",
+              "learn_f16_x2.hip", "learn_bf16_x2.hip", "learn_shared.hip",
               "learn_rules.hpp", "learn_img.hpp", "qnet_layout.hpp", "common.hpp"],
     "sim": ["sim.hip", "sim.hpp", "sim_rules.hpp", "observe.hpp", "common.hpp"],
     # population-based training (score / select / exchange): off the step's path
@@ -101,13 +107,24 @@ def tree_files(root=None):
     return sorted(files, key=lambda p: (os.path.basename(os.path.dirname(p)), os.path.basename(p)))
 
 
-def tree_digest(root=None):
-    """sha256 (hex, 16 chars) over tree_files() (names and contents) and the
-    common compile flags: what libdmdqn_hip.so / libdmdqn_torch.so embed at
-    build time (dmdqn_source_digest) and what _lib.load() checks them against,
-    so a library built from other sources than the tree's is refused."""
+def flag_sets(variant=""):
+    """Every compile flag of a build of `variant`, as one line: the common
+    flags, each file's own (PER_FILE, by name) and the default of the others,
+    the variant's and DMDQN_EXTRA_FLAGS."""
+    per_file = " ".join(f"{n}:{' '.join(f)}" for n, f in sorted(PER_FILE.items()))
+    return " | ".join([" ".join(COMMON), per_file, " ".join(DEFAULT_FP),
+                       " ".join(VARIANT_FLAGS[variant]), " ".join(EXTRA)])
+
+
+def tree_digest(root=None, variant=""):
+    """sha256 (hex, 16 chars) over tree_files() (names and contents) and every
+    compile flag of a build of `variant` (flag_sets: the -D switches of
+    DMDQN_EXTRA_FLAGS among them): what libdmdqn_hip.so / libdmdqn_torch.so
+    embed at build time (dmdqn_source_digest) and what _lib.load() checks them
+    against, so a library built from other sources than the tree's, or from
+    these sources with other switches (an A/B build), is refused."""
     import hashlib
-    h = hashlib.sha256(" ".join(COMMON).encode())
+    h = hashlib.sha256(flag_sets(variant).encode())
     for p in tree_files(root):
         h.update(os.path.basename(p).encode())
         with open(p, "rb") as f:
@@ -192,7 +209,7 @@ def build_torch_ext(force=False, verbose=True, variant=""):
     deps = [TORCH_EXT, os.path.join(LIBDIR, libname(variant))] + _headers()
     abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
     flags = ["-O2", "-fPIC", "-std=c++17", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
-             f'-DDMDQN_SOURCE_DIGEST="{tree_digest()}"',
+             f'-DDMDQN_SOURCE_DIGEST="{tree_digest(variant=variant)}"',
              f"-D_GLIBCXX_USE_CXX11_ABI={abi}", f"-I{tdir}/include",
              f"-I{tdir}/include/torch/csrc/api/include", "-I/opt/rocm/include"]
     stamp = so + ".flags"
@@ -224,7 +241,7 @@ def build(force=False, verbose=True, variant=""):
     with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         results = list(ex.map(lambda s: _compile(s, force, variant), srcs))
     so = os.path.join(LIBDIR, libname(variant))
-    results.append(_digest_object(variant, tree_digest()))
+    results.append(_digest_object(variant, tree_digest(variant=variant)))
     objs = [o for o, _ in results]
     if force or any(ch for _, ch in results) or not os.path.exists(so):
         cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", so] + objs

@@ -36,14 +36,15 @@ int dbg_flags_sim();
 int dbg_flags_rng();
 int dbg_flags_learn();
 int dbg_flags_replay();
-namespace f16k { int dbg_flags(); }
-namespace bf16k { int dbg_flags(); }
+namespace f16k { int dbg_flags(); int dbg_flags_x2(); }
+namespace bf16k { int dbg_flags(); int dbg_flags_x2(); }
 }  // namespace dmdqn
 
 extern "C" int dmdqn_debug_status(void) {
     using namespace dmdqn;
-    const int f[6] = {dbg_flags_sim(), dbg_flags_rng(), dbg_flags_learn(), f16k::dbg_flags(),
-                      bf16k::dbg_flags(), dbg_flags_replay()};
+    const int f[8] = {dbg_flags_sim(), dbg_flags_rng(), dbg_flags_learn(), f16k::dbg_flags(),
+                      bf16k::dbg_flags(), dbg_flags_replay(), f16k::dbg_flags_x2(),
+                      bf16k::dbg_flags_x2()};
     int v = 0;
     for (int x : f) {
         if (x < 0) return -1;

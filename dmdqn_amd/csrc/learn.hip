@@ -408,6 +408,12 @@ __global__ void __launch_bounds__(256) k_q_argmax(const float *params, size_t ps
 // learn_f16.hip / learn_bf16.hip; hp: never null (a block of null arrays = none)
 int launch_learn_f16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, hipStream_t s);
 int launch_learn_bf16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, hipStream_t s);
+int launch_learn_pair_f16(const dmdqn_learn_args *a0, const dmdqn_learn_args *a1,
+                          const dmdqn_agent_hparams *hp0, const dmdqn_agent_hparams *hp1, bool soft,
+                          hipStream_t s);
+int launch_learn_pair_bf16(const dmdqn_learn_args *a0, const dmdqn_learn_args *a1,
+                           const dmdqn_agent_hparams *hp0, const dmdqn_agent_hparams *hp1,
+                           bool soft, hipStream_t s);
 int launch_learn_grad_f16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, float *grad,
                           hipStream_t s);
 int launch_learn_grad_bf16(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, float *grad,
@@ -568,6 +574,52 @@ extern "C" int dmdqn_learn(const dmdqn_learn_args *a, void *stream) {
 extern "C" int dmdqn_learn_hp(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp,
                               void *stream) {
     return learn_entry("dmdqn_learn_hp", a, hp, stream);
+}
+
+// Two consecutive learns of every agent in one launch (include/dmdqn.h).
+extern "C" int dmdqn_learn_pair(const dmdqn_learn_args *a0, const dmdqn_learn_args *a1,
+                                const dmdqn_agent_hparams *hpp0, const dmdqn_agent_hparams *hpp1,
+                                void *stream) {
+    const char *who = "dmdqn_learn_pair";
+    DMDQN_REQUIRE(a0 && a1, "%s: null args", who);
+    dmdqn_agent_hparams hp0, hp1;
+    if (int rc = check_hparams(who, hpp0, &hp0)) return rc;
+    if (int rc = check_hparams(who, hpp1, &hp1)) return rc;
+    if (int rc = check_tau(who, a0->tau, a0->one_minus_tau, true)) return rc;
+    if (int rc = check_tau(who, a1->tau, a1->one_minus_tau, true)) return rc;
+    if (int rc = check_learn_args(a0)) return rc;
+    if (int rc = check_learn_args(a1)) return rc;
+    DMDQN_REQUIRE(a0->params == a1->params && a0->adam_m == a1->adam_m &&
+                      a0->adam_v == a1->adam_v && a0->target == a1->target &&
+                      a0->target_h == a1->target_h && a0->ring_s == a1->ring_s &&
+                      a0->ring_n == a1->ring_n && a0->ring_a == a1->ring_a &&
+                      a0->ring_d == a1->ring_d && a0->ring_r == a1->ring_r && a0->NA == a1->NA &&
+                      a0->cap == a1->cap,
+                  "%s: the two learns must share params, adam_m, adam_v, target, target_h, the "
+                  "rings, NA and cap", who);
+    DMDQN_REQUIRE((a0->precision == 1 || a0->precision == 2) && a1->precision == a0->precision &&
+                      a0->hidden == 128 && a1->hidden == 128 && a0->P == a1->P,
+                  "%s: precision %d / %d, hidden %d / %d (16-bit learns of hidden 128 only)", who,
+                  a0->precision, a1->precision, a0->hidden, a1->hidden);
+    DMDQN_REQUIRE(a0->row_format == DMDQN_ROWS_I8 && a1->row_format == DMDQN_ROWS_I8,
+                  "%s: int8 replay rows only", who);
+    DMDQN_REQUIRE(a0->target_h, "%s: needs the 16-bit target shadow (target_h)", who);
+    DMDQN_REQUIRE(!a0->sync_target && !a1->sync_target,
+                  "%s: a learn with sync_target runs as a single launch (dmdqn_learn)", who);
+    const bool soft0 = a0->tau > 0.0f || hp0.tau, soft1 = a1->tau > 0.0f || hp1.tau;
+    DMDQN_REQUIRE(soft0 == soft1, "%s: one learn has a soft target update, the other has not",
+                  who);
+    DMDQN_REQUIRE((a0->qstats != nullptr) == (a1->qstats != nullptr),
+                  "%s: qstats for both learns or for neither", who);
+    // outputs of one learn each: the second learn must not write over the first's
+    DMDQN_REQUIRE((!a0->loss || a0->loss != a1->loss) && (!a0->qstats || a0->qstats != a1->qstats) &&
+                      (!a0->rn_out || a0->rn_out != a1->rn_out),
+                  "%s: loss, qstats and rn_out must be buffers of each learn's own", who);
+    DMDQN_REQUIRE(!a0->stamps && !a1->stamps,
+                  "%s: stamps (one phase record per workgroup) take a single launch", who);
+    return a0->precision == 1
+               ? launch_learn_pair_f16(a0, a1, &hp0, &hp1, soft0, as_stream(stream))
+               : launch_learn_pair_bf16(a0, a1, &hp0, &hp1, soft0, as_stream(stream));
 }
 
 static int learn_grad_entry(const char *who, const dmdqn_learn_args *a,

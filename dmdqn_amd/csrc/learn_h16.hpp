@@ -12,7 +12,9 @@
 //   * dL/dQ rounded to h16 (the gradient of the learn's tf.cast);
 //   * dH = h16(dZ W^T) masked by relu; dW = h16(X^T dZ), db = h16(sum dZ):
 //     the gradients Adam receives are 16-bit values (no loss scaling).
-// The includer defines DMDQN_H16_BF16 (0 or 1) first.
+// The includer defines DMDQN_H16_BF16 (0 or 1) first, and DMDQN_H16_PAIR 1 to
+// get the paired learn (k_learn_*_x2 and its launcher) in place of the single
+// learn's kernels and launchers (learn_f16_x2.hip, learn_bf16_x2.hip).
 //
 // One workgroup (8 waves) per agent, TWO workgroups per CU: 74 KB of LDS and
 // <= 128 VGPRs, so one agent's HBM phases (weight fragments, replay gather,
@@ -49,6 +51,8 @@
 #define H16_T __bf16
 #define H16_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
 #define H16_LEARN_KERNEL k_learn_bf16
+#define H16_LEARN_PAIR_KERNEL k_learn_bf16_x2
+#define H16_LAUNCH_PAIR launch_learn_pair_bf16
 #define H16_LAUNCH launch_learn_bf16
 #define H16_LAUNCH_GRAD launch_learn_grad_bf16
 #define H16_LAUNCH_ADAM launch_adam_agents_bf16
@@ -59,6 +63,8 @@
 #define H16_T _Float16
 #define H16_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16
 #define H16_LEARN_KERNEL k_learn_f16
+#define H16_LEARN_PAIR_KERNEL k_learn_f16_x2
+#define H16_LAUNCH_PAIR launch_learn_pair_f16
 #define H16_LAUNCH launch_learn_f16
 #define H16_LAUNCH_GRAD launch_learn_grad_f16
 #define H16_LAUNCH_ADAM launch_adam_agents_f16
@@ -881,161 +887,11 @@ __device__ __forceinline__ void bwd_dz1(h16 *R1, const uint32_t *mask, const f32
 // loads and SGPR values, uniform per workgroup) -- a compile-time flag, so the
 // scalar instantiations never read hp and keep their code, and the Adam streams
 // of the per-agent ones carry no branch either.
+#if !DMDQN_H16_PAIR
 template <bool QSTATS, int TM, bool GOUT, bool XF = false, bool TS = true, bool HP = false>
 __global__ void __launch_bounds__(512, 4) H16_LEARN_KERNEL(dmdqn_learn_args a, float *gout,
                                                            dmdqn_agent_hparams hp) {
-    LEARN_SMEM_SETUP;
-    const int agent = blockIdx.x;
-    if constexpr (HP) hp_apply(a, hp, agent);
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, lr = l & 15, lg = l >> 4;
-    const size_t Pz = (size_t)L::P;
-    float *Wp = a.params + agent * Pz, *Mp = a.adam_m + agent * Pz, *Vp = a.adam_v + agent * Pz;
-    float *Tp = a.target + agent * Pz;
-    const size_t Ph = (Pz + 7) / 8 * 8;
-    h16 *TH = TS ? reinterpret_cast<h16 *>(a.target_h) + agent * Ph : nullptr;
-    static_assert(TM != TGT_SOFT || (TS && !GOUT), "soft: with the shadow, fused learn only");
-    const AdamC AK{a.alpha, a.c1, a.c2, a.eps, GOUT ? TGT_NONE : TM, TH, GOUT,
-                   GOUT ? gout + agent * Pz : nullptr, a.tau, a.one_minus_tau};
-    STAMP(0);
-    // Issue order (vmcnt is in-order): the deque positions, the output layers,
-    // then the target's fragments -- so the slot computation waits only for
-    // the positions and the S' row gather goes out while the fragments land
-    // (round 4 stored the output layers to LDS right after issuing the
-    // fragments: the head then waited for every fragment before the gather)
-    const int pos = batch_pos(a, agent);
-    const OutStage so_on = stage_out_load(Wp);
-    OutStage so_tg;
-    if constexpr (TS) so_tg = stage_out_load(TH);
-    else so_tg = stage_out_load(Tp);
-    Frags fr;
-    if constexpr (TS) load_frags(TH, fr);  // in flight during the z-score + gather
-    else load_frags(Tp, fr);
-
-    // ---- slots, X(S') + metadata from the s' rows, z-score (the output
-    // layers' LDS images are synced by its barriers)
-    batch_head<XF>(a, agent, pos, R2, S, [&]() {
-        stage_out_store(so_on, W3L, B3L);
-        stage_out_store(so_tg, W3L + NACT * H, B3L + NACT);
-    });
-    STAMP(1);
-    STAMP(2);
-    // ---- target(S') -> z3 ; online(S') -> Q ; y
-    // target forward keeps X(S') in R2; the online net's fragments (reused by
-    // both online forwards) load layer by layer as the target's die
-    const float *Wpc = Wp;
-    // Buffer plan: target X=R2 -> H1 R1 -> H2 R1 (hold; X survives) ;
-    // online S': X=R2 -> H1 R1 -> H2 R2 over the dead X (no hold), the S rows
-    // issued after layer 1 land in R1 once layer 2 is done ; training forward:
-    // X=R1 -> H1 R2 -> H2 R1 over X (no hold).  The backward then finds H1 in R2
-    // and H2 in R1: it runs on the swapped pair (P1, P2) = (R2, R1).
-    forward_x<true>(fr, tg, R2, R1, R1, S.z3, [Wpc](Frags &f) { load_w1(Wpc, f); },
-                    [Wpc](Frags &f) { load_w2(Wpc, f); });
-    STAMP(3);
-    float *qo = (float *)DQ;
-    RowsT<XF> gs;
-    forward_x<false>(fr, on, R2, R1, R2, qo,
-                     [&](Frags &) { gather_x<XF>(a, agent, false, S.slot, gs); }, NoHook{},
-                     [&]() { commit_x<XF>(R1, gs); });
-    STAMP(4);
-    STAMP(5);
-    ddqn_target(a, qo, S);
-    STAMP(6);
-    forward_x<false>(fr, on, R1, R2, R1, S.z3);
-    h16 *const P1 = R2, *const P2 = R1;
-    STAMP(7);
-    const half8 ones = ones8();
-    loss_dq<QSTATS>(a, agent, DQ, S);
-    // ---- dW3[k][a] = H2^T . DQ (wave w: k-tile w) ; db3 (wave 0)
-    {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, gb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int b0 = 0; b0 < B_; b0 += 32) {
-            half8 dqf = frag_tr(DQ, 16, b0, 0);
-            acc = mfma(frag_tr_h(P2, b0, 16 * w), dqf, acc);
-            gb = mfma(ones, dqf, gb);  // every wave (no MFMA under divergent control)
-        }
-        if (lr < NACT) {
-            // rows k = 16w + 4lg + e (consecutive), column a: W3T[a][k..k+3]
-            adam4(Wp, Mp, Vp, Tp, L::oW3T + (size_t)lr * H + 16 * w + 4 * lg, acc, AK);
-            if (w == 0 && lg == 0) adam1(Wp, Mp, Vp, Tp, L::ob3 + lr, gb[0], AK);
-        }
-    }
-    __syncthreads();  // dW3 read H2; dZ2 overwrites it
-    STAMP(8);
-    bwd_dz2(P2, on, S);
-    STAMP(9);
-    h1_mask(P1, mask);  // the DQ region is free now
-    // ---- dW2[j][k] = H1^T . dZ2 (wave w: j-tile w, 8 k-tiles) ; db2 (k-tile w) ; Adam
-    {
-        f32x4 g2[8], gb = {0.f, 0.f, 0.f, 0.f};
-        // rows j = 16w + 4lg + e, column k = 16t + lr  ->  W2T[k][j..j+3]
-        adam_pipe<4, 2, false>(
-            Wp, Mp, Vp, Tp,
-            [&](int t) { return (size_t)L::oW2T + qn_wt(16 * t + lr, 16 * w + 4 * lg, H); }, g2,
-            AK, [&]() {
-#pragma unroll
-                for (int t = 0; t < 8; t++) g2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int b0 = 0; b0 < B_; b0 += 32) {
-                    const half8 av = frag_tr_h(P1, b0, 16 * w);
-                    gb = mfma(ones, frag_tr_h(P2, b0, 16 * w), gb);
-#pragma unroll
-                    for (int t = 0; t < 8; t++) g2[t] = mfma(av, frag_tr_h(P2, b0, 16 * t), g2[t]);
-                }
-                // H1 fully consumed (dW2, mask): P1 becomes the W2^T image now,
-                // from the register copy of old W2 (fr.w2), dead during Adam
-                __syncthreads();
-                w2t_image(P1, fr);
-            });
-        const int tx = fresh_tid();  // (16w + lr kept from the head spilled)
-        if ((tx & 63) < 16) adam1(Wp, Mp, Vp, Tp, L::ob2 + (tx >> 6) * 16 + (tx & 15), gb[0], AK);
-    }
-    __syncthreads();  // W2^T image complete
-    f32x4 d1[8];
-    bwd_dh1_from_image(P1, P2, d1);
-    {
-        RowsT<XF> gx;  // X(S) again for dW1 (P2 is free)
-        gather_x<XF>(a, agent, false, S.slot, gx);
-        commit_x<XF>(P2, gx);
-    }
-    STAMP(10);
-    bwd_dz1(P1, mask, d1);
-    __syncthreads();
-    STAMP(11);
-    // ---- dW1[i][j] = X^T . dZ1 (wave w: j-tile w, 6 i-tiles) ; db1 (j-tile w)
-    {
-        const int tx = fresh_tid(), lr = tx & 15, lg = (tx & 63) >> 4;
-        f32x4 g1[6], gb = {0.f, 0.f, 0.f, 0.f};
-        // rows i = 16t + 4lg + e, column j = 16w + lr -> W1T[j][i..i+3]; tile 5
-        // holds features 80..95: lanes lg < 2 (80..87) update in the pipe, lane
-        // lg = 2's first row is feature 88 (the W1T column, below), the rest
-        // (89..95) do not exist
-        adam_pipe<2, 3, true>(
-            Wp, Mp, Vp, Tp,
-            [&](int t) { return (size_t)L::oW1T + qn_w1<H>(16 * w + lr, t < 5 || lg < 2 ? 16 * t + 4 * lg : 0); },
-            g1, AK, [&]() {
-#pragma unroll
-                for (int t = 0; t < 6; t++) g1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int b0 = 0; b0 < B_; b0 += 32) {
-                    const half8 bv = frag_tr_h(P1, b0, 16 * w);
-                    gb = mfma(ones, bv, gb);
-#pragma unroll
-                    for (int t = 0; t < 6; t++)
-                        g1[t] = mfma(frag_tr_h<DP>(P2, b0, 16 * t), bv, g1[t]);
-                }
-            },
-            [&](int t) { return t < 5 || lg < 2; });
-        // b1[j] (lanes lg = 0: every row of the ones-MFMA holds the column sum)
-        // and W1T[j][88] (lanes lg = 2, row 88 of tile 5)
-        if (lg == 0 || lg == 2)
-            adam1(Wp, Mp, Vp, Tp, (lg == 0 ? L::ob1 : L::oW1X) + 16 * w + lr,
-                  lg == 0 ? gb[0] : g1[5][0], AK);
-    }
-    if (a.stamps) {
-        __syncthreads();
-        STAMP(12);
-    }
+#include "learn_h16_body.hpp"
 }
 
 // The split learn's second launch: Keras-3 Adam (keras_adam_el, the fused kernel's
@@ -1186,5 +1042,88 @@ int H16_LAUNCH_ADAM(const dmdqn_learn_args *a, const dmdqn_agent_hparams *hp, co
     DMDQN_LAUNCH_CHECK("k_adam_agents_" H16_NAME);
     return DMDQN_OK;
 }
+
+#else  // DMDQN_H16_PAIR: the paired learn alone (learn_f16_x2.hip, learn_bf16_x2.hip)
+
+// Two consecutive learns of every agent in one launch: workgroup `agent` runs
+// learn a0, then learn a1, on the same LDS block.  a0 and a1 share the network,
+// Adam slots, target, shadow and rings and differ in what a step fixes (idx,
+// start, loss / qstats / rn_out, the Adam constants, hp's Adam factors), so the
+// second learn re-reads W, m, v (and, soft, T / TH) one workgroup lifetime
+// after the first wrote them instead of one whole launch later.  Per agent the
+// arithmetic and its order are those of two launches: the same bits.  Between
+// the two bodies the first one's global stores are made visible to every wave
+// of the workgroup (workgroup-scope release / acquire around the barrier: the
+// waves share the CU's vector L1, which is write-through) and the barrier also
+// frees the LDS block.  int8 rows, target shadow, fused Adam; TM: TGT_NONE or
+// TGT_SOFT (a hard sync runs as a single launch).
+struct PairArgs {
+    dmdqn_learn_args a[2];
+    dmdqn_agent_hparams hp[2];
+};
+
+template <bool QSTATS, int TM, bool HP>
+__global__ void __launch_bounds__(512, 4) H16_LEARN_PAIR_KERNEL(PairArgs p) {
+    static_assert(TM == TGT_NONE || TM == TGT_SOFT, "pair: no hard sync");
+    constexpr bool GOUT = false, XF = false, TS = true;
+    float *const gout = nullptr;
+    // Two rounds over ONE copy of the body, entered a second way that is never
+    // taken (NA > 0: the host checks it), so that the compiler sees no natural
+    // loop.  As two copies in a row the second one's lane-derived addresses
+    // were commoned with the first's, as a plain loop they were hoisted out
+    // of it, and either way they were kept live across the body and spilled
+    // (400-600 B of scratch per lane against the single kernel's 0-56).  The
+    // backend's own loop-invariant code motion does the same once it has made
+    // a loop of this (120-180 B): the paired learn's files are compiled with
+    // -mllvm -disable-machine-licm (build.py PER_FILE), which is why they are
+    // files of their own.  With both, the figures are the single kernel's.
+    int i = 0;
+    if (p.a[0].NA < 0) goto between;
+again : {
+    dmdqn_learn_args a = p.a[i];
+    const dmdqn_agent_hparams hp = p.hp[i];
+#include "learn_h16_body.hpp"
+}
+between:
+    __threadfence_block();
+    __syncthreads();
+    if (++i < 2) goto again;
+}
+
+DMDQN_DBG_READER(dbg_flags_x2)
+
+}  // namespace H16K
+
+// dmdqn_learn_pair: the learns a0 then a1 of every agent in one launch (the
+// entry point has checked what the two share).  A soft pair always runs the
+// fused update (TGT_SOFT): there is no place between the two bodies for the
+// flat k_target_soft launch, and the bits are the same.
+int H16_LAUNCH_PAIR(const dmdqn_learn_args *a0, const dmdqn_learn_args *a1,
+                    const dmdqn_agent_hparams *hp0, const dmdqn_agent_hparams *hp1, bool soft,
+                    hipStream_t s) {
+    DMDQN_REQUIRE(a0->hidden == 128 && a0->P == H16K::L::P,
+                  "dmdqn_learn_pair: precision %d (" H16_NAME ") needs hidden=128 (P=%d)",
+                  a0->precision, H16K::L::P);
+    using namespace H16K;
+    const bool qs = a0->qstats != nullptr, hp = hp_any(*hp0) || hp_any(*hp1);
+    using PairKernel = void (*)(PairArgs);
+    PairKernel kern;
+    if (soft)
+        kern = hp ? (qs ? H16_LEARN_PAIR_KERNEL<true, TGT_SOFT, true>
+                        : H16_LEARN_PAIR_KERNEL<false, TGT_SOFT, true>)
+                  : (qs ? H16_LEARN_PAIR_KERNEL<true, TGT_SOFT, false>
+                        : H16_LEARN_PAIR_KERNEL<false, TGT_SOFT, false>);
+    else
+        kern = hp ? (qs ? H16_LEARN_PAIR_KERNEL<true, TGT_NONE, true>
+                        : H16_LEARN_PAIR_KERNEL<false, TGT_NONE, true>)
+                  : (qs ? H16_LEARN_PAIR_KERNEL<true, TGT_NONE, false>
+                        : H16_LEARN_PAIR_KERNEL<false, TGT_NONE, false>);
+    const PairArgs p{{*a0, *a1}, {*hp0, *hp1}};
+    hipLaunchKernelGGL(kern, dim3(a0->NA), dim3(512), 0, s, p);
+    DMDQN_LAUNCH_CHECK("k_learn_" H16_NAME "_x2");
+    return DMDQN_OK;
+}
+
+#endif  // DMDQN_H16_PAIR
 
 }  // namespace dmdqn

@@ -476,6 +476,51 @@ void learn_step_hp(const Tensor &ring_s, const Tensor &ring_n, const Tensor &rin
     check(dmdqn_learn_hp(&a, &hp, stream_of(params)), "dmdqn_learn_hp");
 }
 
+// Two consecutive learns of every agent in one launch (dmdqn_learn_pair): the
+// shared tensors once, then what a step fixes for each learn -- idx, loss,
+// start, adam = [alpha, c1, c2, eps], qstats, rn_out and, with per-agent
+// hyperparameters, factors = [adam_s, adam_d].
+void learn_pair(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
+                const Tensor &ring_d, const Tensor &ring_r, Tensor &params, Tensor &adam_m,
+                Tensor &adam_v, Tensor &target, Tensor &target_h, const Tensor &idx0,
+                const Tensor &idx1, Tensor &loss0, Tensor &loss1, int64_t start0, int64_t start1,
+                int64_t hidden, int64_t precision, double gamma, at::ArrayRef<double> adam0,
+                at::ArrayRef<double> adam1, int64_t loss_kind, const OptT &qstats0,
+                const OptT &qstats1, const OptT &rn_out0, const OptT &rn_out1, double tau,
+                double one_minus_tau, const OptT &lr, const OptT &gamma_a, const OptT &tau_a,
+                const OptT &one_minus_tau_a, at::ArrayRef<double> factors0,
+                at::ArrayRef<double> factors1) {
+    const int64_t NA = loss0.numel();
+    TORCH_CHECK(adam0.size() == 4 && adam1.size() == 4, "adam0 / adam1: [alpha, c1, c2, eps]");
+    TORCH_CHECK(factors0.size() == 2 && factors1.size() == 2, "factors0 / factors1: [s, d]");
+    TORCH_CHECK(loss1.numel() == NA, "loss0 and loss1 must both be [NA]");
+    const OptT th = target_h;
+    dmdqn_learn_args a[2];
+    dmdqn_agent_hparams hp[2];
+    for (int i = 0; i < 2; i++) {
+        const at::ArrayRef<double> &ad = i ? adam1 : adam0, &fa = i ? factors1 : factors0;
+        const OptT lo = i ? loss1 : loss0;
+        a[i] = make_learn(ring_s, ring_n, ring_a, ring_d, ring_r, i ? idx1 : idx0, params, adam_m,
+                          adam_v, target, th, lo, i ? start1 : start0, hidden, precision, false,
+                          gamma, ad[0], ad[1], ad[2], ad[3], loss_kind, i ? qstats1 : qstats0,
+                          i ? rn_out1 : rn_out0, std::nullopt, std::nullopt, NA, NA);
+        a[i].tau = (float)tau;
+        a[i].one_minus_tau = (float)one_minus_tau;
+        hp[i] = dmdqn_agent_hparams{};
+        hp[i].lr = optr<const float>(lr, at::kFloat, "lr", NA);
+        hp[i].gamma = optr<const float>(gamma_a, at::kFloat, "gamma_a", NA);
+        hp[i].tau = optr<const float>(tau_a, at::kFloat, "tau_a", NA);
+        hp[i].one_minus_tau = optr<const float>(one_minus_tau_a, at::kFloat, "one_minus_tau_a", NA);
+        hp[i].adam_s = (float)fa[0];
+        hp[i].adam_d = (float)fa[1];
+    }
+    for (const OptT *t : {&lr, &gamma_a, &tau_a, &one_minus_tau_a})
+        TORCH_CHECK(!t->has_value() || (*t)->device() == params.device(),
+                    "per-agent hyperparameters must be on the device of params");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    check(dmdqn_learn_pair(&a[0], &a[1], &hp[0], &hp[1], stream_of(params)), "dmdqn_learn_pair");
+}
+
 void learn_shared_grad(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
                        const Tensor &ring_d, const Tensor &ring_r, const Tensor &idx,
                        const Tensor &params, const Tensor &target, const Tensor &target_h,
@@ -692,6 +737,13 @@ void learn_step_hp_meta(const Tensor &, const Tensor &, const Tensor &, const Te
                         double, double, double, int64_t, const OptT &, const OptT &, const OptT &,
                         const OptT &, const OptT &, const OptT &, double, double, const OptT &,
                         const OptT &, const OptT &, const OptT &, double, double) {}
+void learn_pair_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                     Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, const Tensor &,
+                     const Tensor &, Tensor &, Tensor &, int64_t, int64_t, int64_t, int64_t, double,
+                     at::ArrayRef<double>, at::ArrayRef<double>, int64_t, const OptT &,
+                     const OptT &, const OptT &, const OptT &, double, double, const OptT &,
+                     const OptT &, const OptT &, const OptT &, at::ArrayRef<double>,
+                     at::ArrayRef<double>) {}
 void learn_shared_grad_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                             const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                             const Tensor &, const Tensor &, Tensor &, int64_t, double, int64_t,
@@ -775,6 +827,16 @@ TORCH_LIBRARY(dmdqn, m) {
           "Tensor? xs=None, Tensor? xn=None, float tau=0.0, float one_minus_tau=1.0, "
           "Tensor? lr=None, Tensor? gamma_a=None, Tensor? tau_a=None, "
           "Tensor? one_minus_tau_a=None, float adam_s=1.0, float adam_d=1.0) -> ()");
+    // two consecutive DQNAgent.learn calls of every agent in one launch (dmdqn_learn_pair)
+    m.def("learn_pair(Tensor ring_s, Tensor ring_n, Tensor ring_a, Tensor ring_d, Tensor ring_r, "
+          "Tensor(a!) params, Tensor(b!) adam_m, Tensor(c!) adam_v, Tensor(d!) target, "
+          "Tensor(e!) target_h, Tensor idx0, Tensor idx1, Tensor(f!) loss0, Tensor(g!) loss1, "
+          "int start0, int start1, int hidden, int precision, float gamma, float[] adam0, "
+          "float[] adam1, int loss_kind, Tensor(h!)? qstats0=None, Tensor(i!)? qstats1=None, "
+          "Tensor(j!)? rn_out0=None, Tensor(k!)? rn_out1=None, float tau=0.0, "
+          "float one_minus_tau=1.0, Tensor? lr=None, Tensor? gamma_a=None, Tensor? tau_a=None, "
+          "Tensor? one_minus_tau_a=None, float[] factors0=[1.0, 1.0], "
+          "float[] factors1=[1.0, 1.0]) -> ()");
     // C5: per-agent gradients of one shared net, summed
     m.def("learn_shared_grad(Tensor ring_s, Tensor ring_n, Tensor ring_a, Tensor ring_d, "
           "Tensor ring_r, Tensor idx, Tensor params, Tensor target, Tensor target_h, "
@@ -822,6 +884,7 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("env_step", &env_step);
     m.impl("learn_step", &learn_step);
     m.impl("learn_step_hp", &learn_step_hp);
+    m.impl("learn_pair", &learn_pair);
     m.impl("learn_shared_grad", &learn_shared_grad);
     m.impl("adam", &adam);
     m.impl("adam_slabs", &adam_slabs);
@@ -849,6 +912,7 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("env_step", &env_step_meta);
     m.impl("learn_step", &learn_step_meta);
     m.impl("learn_step_hp", &learn_step_hp_meta);
+    m.impl("learn_pair", &learn_pair_meta);
     m.impl("learn_shared_grad", &learn_shared_grad_meta);
     m.impl("adam", &adam_meta);
     m.impl("adam_slabs", &adam_slabs_meta);

@@ -46,6 +46,19 @@ sequential order, so results are bit-identical (tests/test_gpu_overlap.py).
             1) waits for learn t's weights.
               side:  [wait the newest marked learn <= t-1] env_step_{t+1} sample_{t+1} (ev_env)
               main:  [wait ev_env of t] learn_t
+            16-bit independent nets run their learns in PAIRS (pair_learns,
+            default on): learn t is begun and held back, and the next call
+            launches learns t and t+1 as one kernel (dmdqn_learn_pair; the second
+            learn re-reads the weights and Adam slots while they are on the chip;
+            the same bits).  Hard target syncs, collect_stats steps, a learn_hook
+            and the agent's diagnostics buffers keep single launches.
+            CHANGES WHAT step() LEAVES: after a call that held its learn back,
+            agent.params / adam_m / adam_v / target and agent.loss are one learn
+            behind until the next call.  Read them through last_loss or after
+            sync_outputs() / synchronize() (they launch the held-back learn), or
+            pass pair_learns=False; a loop that does so after EVERY step runs
+            every learn alone and gains nothing from pairing.
+              main:  [wait ev_env of t] -        [wait ev_env of t+1] learn_{t,t+1}
             With a CU-masked side stream (bench --cu-split) the two split the
             chip.  side_learn=m runs the learn of the last m agents on the side
             stream behind its env step and draws (those CUs idle otherwise):
@@ -77,7 +90,10 @@ What a step returns or exposes per step (obs, reward, loss, agent.actions,
 agent.idx) is fresh or double-buffered, so the caller may read it on its own
 stream between steps (under "env" with side_learn, read the loss through
 last_loss, or call sync_outputs() before reading agent tensors: the side
-learn's part is waited for lazily, except on collect_stats steps).  Persistent env/agent state (sim arrays, RNG streams) is
+learn's part is waited for lazily, except on collect_stats steps; with paired
+learns a held-back learn is launched by the same two, by synchronize(),
+quiesce() and join_streams(): agent.loss and the nets read without them may
+lag one learn).  Persistent env/agent state (sim arrays, RNG streams) is
 advanced by the next step's side stream without waiting for such reads: read
 it host-blocking (.cpu()), and call join_streams() after writing it.
 """
@@ -95,6 +111,29 @@ from .env import EnvConfig, TrafficEnv
 SCHEDULES = ("none", "sample", "full", "env", "learn")
 
 
+def pair_action(pending, plain, next_sync):
+    """What a call of the paired "env" schedule does with the learn it has begun
+    (pending: a held-back learn of the call before exists; plain: this learn may
+    share a launch -- no metrics, no timing hook, no hard sync; next_sync: the
+    learn after it is a hard sync): "pair" (one launch for both), "both" (the
+    held-back one, then this one, a launch each), "hold" (launch nothing: the
+    next call pairs it) or "single"."""
+    if pending:
+        return "pair" if plain else "both"
+    return "hold" if plain and not next_sync else "single"
+
+
+def pair_mark_due(j, last_mark, spare, mark_every=False):
+    """Whether the paired "env" schedule marks call j (all learns up to j's are
+    launched), the newest mark being of call last_mark (-1: none yet).  A call
+    that holds its learn back cannot be marked, but of two calls in a row one
+    can: the call after a held-back one launches both learns, or -- the caller
+    having had the held-back learn launched in between -- marks for it first.
+    So the next chance after j may be j + 2, and marks are at most `spare`
+    calls apart when j is marked from j - last_mark >= spare - 1 on."""
+    return mark_every or j - last_mark >= spare - 1
+
+
 @dataclass
 class StepStats:
     loss_launched: bool
@@ -104,7 +143,7 @@ class StepStats:
 class Trainer:
     def __init__(self, env_cfg: EnvConfig = None, agent_cfg: AgentConfig = None, device="cuda",
                  overlap="none", side_stream=None, split_learn=False, fused=True,
-                 war_events=True, side_learn=0, mark_every_learn=False):
+                 war_events=True, side_learn=0, mark_every_learn=False, pair_learns=True):
         # a sweep (AgentConfig.sweep) is checked before any device work, which
         # starts with the env below; BatchedDQN, usable without a Trainer,
         # expands the grid again for itself (host work on a few list entries)
@@ -200,6 +239,21 @@ class Trainer:
         self._calls = 0
         self.n_marks = 0  # marked calls that learned (tests: every spare-th learn)
         self._mark_every = bool(mark_every_learn)  # A/B: a marker behind every learn
+        # overlap "env": learns in pairs (pair_learns, default on).  The env
+        # step, the store and the draws of a step run ahead of its learn, so a
+        # learn's inputs exist one call before the next learn's do: the learn of
+        # a call is begun (agent.learn_begin: its draws, buffers, Adam constants
+        # and ring window are fixed) and held back, and the next call launches
+        # both as one dmdqn_learn_pair -- the same bits, the second learn's
+        # weights, Adam slots and target still on the chip.  _pending: the token
+        # of the held-back learn; _flush_pending() launches it alone (every
+        # method that hands state or outputs to the caller does).
+        self.pair_learns = bool(pair_learns)
+        self._pending = None
+        self._pending_stream = None  # the learn stream of the call that held it back
+        self._last_mark = -1  # the call of the newest mark (paired marks: see the step)
+        self._held = -2       # the last call that held its learn back
+        self._pairs_fixed = None
         self.obs = self.env.reset()
         self.episode = 0
         self.step_count = 0
@@ -374,6 +428,19 @@ class Trainer:
         k = self._calls
         self._calls += 1
         spare = agent.ring.slots - agent.ring.cap
+        if self._held == k - 1 and self._pending is None and pair_mark_due(
+                k - 1, self._last_mark, spare, self._mark_every):
+            # paired learns: call k - 1 held its learn back (no mark then) and
+            # the caller has had it launched since (last_loss, sync_outputs,
+            # ...): its mark, due by the rule below, goes behind that launch now
+            # (on the stream that launch went to: the learn stream of call k - 1)
+            ev = self._war_ring[self._war_i]
+            self._war_i = (self._war_i + 1) % len(self._war_ring)
+            ev.record(self._pending_stream or main)
+            self._ev_learn = ev
+            self._marks.append((k - 1, ev))
+            self._last_mark = k - 1
+            self.n_marks += 1
         marks = [m for m in self._marks if m[0] <= k - 2]
         if k - 1 - spare >= 0 and not (marks and marks[-1][0] >= k - 1 - spare):
             # (every call k' has a mark in [k' - 1 - spare, k' - 2]: see below)
@@ -399,7 +466,8 @@ class Trainer:
             self.obs = self._after_step(done, next_obs, info)  # (an episode reset: on side)
             ev_env = torch.cuda.Event()
             ev_env.record(side)
-        learned = agent.learn_begin(collect_stats)  # the draws above, the Adam constants
+        tok = agent.learn_begin(collect_stats)  # the draws above, the Adam constants
+        learned = bool(tok)
         ev_side = None
         if learned and self.side_learn:
             with torch.cuda.stream(side):
@@ -412,12 +480,64 @@ class Trainer:
         # while a main-stream read of them is still queued
         for t in (next_obs, reward, env.local, self.obs):
             t.record_stream(main)
-        loss = None
-        if learned:
-            loss = agent.learn_range(0, agent.NA - self.side_learn)
         war = (self._war_ring is not None and not agent.cfg.count_env_steps
                and agent.current_epsilon() >= 1.0)
-        if war and spare >= 2 and not self._mark_every and k % spare:
+        loss = None
+        pairing = war and self._pairs()
+        if self._pending is not None and self._pending_stream != main:
+            # the caller changed streams between two calls: the held-back learn
+            # goes to the learn stream it was begun for, and this one follows it
+            self._flush_pending()
+        if not pairing or not learned:
+            self._flush_pending()
+            if learned:
+                loss = agent.learn_range(0, agent.NA - self.side_learn)
+        else:
+            # this learn may share a launch: no metrics, no timing hook (it
+            # brackets single launches), no hard sync (another compile-time
+            # variant of the kernel)
+            plain = not (collect_stats or agent.learn_hook or tok.sync)
+            pend, self._pending = self._pending, None
+            loss = tok.loss
+            what = pair_action(pend is not None, plain, tok.next_sync)
+            if what == "pair":
+                agent.learn_pair_range(pend, tok, 0, agent.NA)
+            elif what == "both":
+                agent.learn_range(0, agent.NA, pend)
+                agent.learn_range(0, agent.NA, tok)
+            elif what == "hold":
+                # the next call launches it with its own learn (the loss buffer
+                # is filled then; last_loss launches it at once)
+                self._pending = tok
+                self._pending_stream = main
+                self._held = k
+            else:
+                agent.learn_range(0, agent.NA, tok)
+        if self._pending is not None:
+            # No mark can follow a learn that is not launched: a mark of call j
+            # stands behind the launch that holds learn j (the side stream's
+            # store of call j + 1 + spare, and its reuse of call j's index
+            # buffer, wait for it).  The next call launches and may mark.
+            pass
+        elif pairing:
+            # Marks with held-back learns: a launching call k marks when the
+            # newest mark is of call k - (spare - 1) or older.  A held-back
+            # call k is followed by a launching call k + 1, or its learn is
+            # launched for the caller in between and call k + 1 marks for it
+            # first (at the top): of two calls in a row one can be marked, so
+            # two marks are at most `spare` calls apart and every window
+            # [k' - 1 - spare, k' - 2] holds one (checked at the top of each
+            # call): the side stream runs at most spare - 1 steps ahead of a
+            # held-back learn.
+            if pair_mark_due(k, self._last_mark, spare, self._mark_every):
+                ev = self._war_ring[self._war_i]
+                self._war_i = (self._war_i + 1) % len(self._war_ring)
+                ev.record(main)
+                self._ev_learn = ev
+                self._marks.append((k, ev))
+                self._last_mark = k
+                self.n_marks += learned
+        elif war and spare >= 2 and not self._mark_every and k % spare:
             # under ordering-only events only every spare-th call is marked
             # (whether or not it learned: the mark also orders the side
             # stream's reuse of the per-step output buffers after the caller's
@@ -440,11 +560,13 @@ class Trainer:
             ev.record(main)
             self._ev_learn = ev
             self._marks.append((k, ev))
+            self._last_mark = k
             self.n_marks += learned
         else:
             self._ev_learn = torch.cuda.Event()
             self._ev_learn.record(main)
             self._marks.append((k, self._ev_learn))
+            self._last_mark = k
             self.n_marks += learned
         # the side learn's outputs (its agents' loss, stats and weights) for the
         # caller's stream.  The next learn needs no wait for them: the side
@@ -462,6 +584,39 @@ class Trainer:
         self.last_loss, self.last_reward = loss, reward
         return StepStats(loss is not None, done)
 
+    def _pairs(self):
+        """Whether the "env" schedule runs its learns in pairs: the option, and
+        what dmdqn_learn_pair takes -- 16-bit independent nets on int8 rows in
+        one fused launch on the learn stream (no side learn, no split learn) --
+        with at least two spare ring slots (a held-back learn lags its store by
+        one more call) and without the agent's diagnostics buffers (rn_out,
+        stamps: one buffer each, read after the step that wrote it)."""
+        ag = self.agent
+        if self._pairs_fixed is None:  # what cannot change after construction
+            self._pairs_fixed = (
+                self.pair_learns and self.overlap == "env" and not ag.shared
+                and ag.cfg.precision in ("fp16", "bf16") and ag.ring.row_format == "int8"
+                and ag.ring.slots - ag.ring.cap >= 2 and not self.side_learn)
+        return (self._pairs_fixed and ag.rn_out is None and ag.stamps is None
+                and not ag.split_learn)
+
+    def _flush_pending(self):
+        """Launch a held-back learn (paired learns) alone, on the learn stream of
+        the call that began it -- where its env step and draws were waited for,
+        where the next learns follow it and where its mark is recorded -- and
+        make the current stream, if it is another one, wait for it."""
+        pend, self._pending = self._pending, None
+        if pend is None:
+            return
+        stream = self._pending_stream
+        cur = torch.cuda.current_stream(self.env.device)
+        with torch.cuda.stream(stream):
+            self.agent.learn_range(0, self.agent.NA, pend)
+        if cur != stream:
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            cur.wait_event(ev)
+
     @property
     def last_loss(self):
         """The last learn's per-agent losses (None before the first learn),
@@ -474,9 +629,15 @@ class Trainer:
         self._last_loss = v
 
     def sync_outputs(self):
-        """Make the current stream wait for the last step's side-stream learn
-        (schedule "env" with side_learn), so the agent's loss, stats and
-        weights read on it are complete.  A no-op otherwise."""
+        """Make the agent's loss, stats and weights complete for reads on the
+        current stream.  Schedule "env" with paired learns: a held-back learn
+        is LAUNCHED now (a kernel, on the learn stream of the step that began
+        it; the current stream waits for it) -- so a loop that calls this, or
+        reads last_loss, after every step never pairs.  With side_learn: the
+        current stream waits for the last step's side-stream learn.  A no-op
+        otherwise."""
+        if getattr(self, "_pending", None) is not None:
+            self._flush_pending()
         if getattr(self, "_side_pending", None) is not None:
             torch.cuda.current_stream(self.env.device).wait_event(self._side_pending)
 
@@ -572,5 +733,6 @@ class Trainer:
         """Wait for all device work, and (C5 over RCCL) first for every
         outstanding gradient all-reduce, bounded: a peer that stalled on or
         skipped one raises DistError instead of hanging the synchronize."""
+        self.sync_outputs()  # (a held-back learn of the paired "env" schedule is launched)
         self.agent.drain_collectives()
         torch.cuda.synchronize(self.env.device)

@@ -72,7 +72,9 @@ const char *dmdqn_last_error(void);
  * of one run); dmdqn_learn_args and the entry points without _hp are unchanged.
  * dmdqn_replay_nstep_commit with dmdqn_nstep_args is new -- n-step returns
  * built at the replay store: the learn entry points and their structs are
- * unchanged and receive gamma^n for gamma. */
+ * unchanged and receive gamma^n for gamma.
+ * dmdqn_learn_pair is new -- two consecutive learns of every agent in one
+ * launch; dmdqn_learn and its structs are unchanged. */
 int dmdqn_version(void);
 
 /* The digest of the sources this library was built from (16 hex chars:
@@ -583,6 +585,34 @@ int dmdqn_learn_grad_hp(const dmdqn_learn_args *args, const dmdqn_agent_hparams 
                         void *stream);
 int dmdqn_adam_agents_hp(const dmdqn_learn_args *args, const dmdqn_agent_hparams *hp,
                          const float *grad, void *stream);
+
+/* Two consecutive learns of every agent in ONE launch (two calls of
+ * DQNAgent.learn, dqn_agent.py:328-380, with nothing of the agent's between
+ * them): workgroup `agent` runs the learn of a0, then the learn of a1, so the
+ * second one reads the weights, Adam slots and target one workgroup lifetime
+ * after the first wrote them.  Bit contract: every output -- params, adam_m,
+ * adam_v, target, target_h, both loss arrays, qstats, rn_out -- is what
+ * dmdqn_learn_hp(a0, hp0) followed by dmdqn_learn_hp(a1, hp1) on the same
+ * stream leaves.  The caller must have both learns' inputs before the launch
+ * (idx, the ring window of `start`, the Adam constants).  hp0 / hp1: NULL or a
+ * block as for dmdqn_learn_hp.  Refused on the host (DMDQN_EINVAL, before any
+ * launch), besides what dmdqn_learn_hp refuses for either learn:
+ *   a0 and a1 not sharing params, adam_m, adam_v, target, target_h, ring_s,
+ *   ring_n, ring_a, ring_d, ring_r, NA and cap (they may differ in idx, start,
+ *   loss, qstats, rn_out, gamma, alpha, c1, c2, eps, tau, loss_kind);
+ *   precision other than 1 / 2, or hidden != 128;
+ *   row_format other than DMDQN_ROWS_I8, or target_h == NULL;
+ *   sync_target set in either (the hard copy is a single launch's variant);
+ *   one learn with a soft target update (tau > 0 or hp tau) and one without;
+ *   qstats given for one learn only;
+ *   loss, qstats or rn_out given as the SAME buffer for both learns (the
+ *   second learn would write over the first's);
+ *   stamps given in either (one record per workgroup: a single launch's).
+ * A soft pair always runs the update fused into the Adam epilogue, whatever
+ * DMDQN_OPT_SOFT_PATH says (the same bits). */
+int dmdqn_learn_pair(const dmdqn_learn_args *a0, const dmdqn_learn_args *a1,
+                     const dmdqn_agent_hparams *hp0, const dmdqn_agent_hparams *hp1,
+                     void *stream);
 
 /* dmdqn_target_soft_update (DQNAgent.update_target_network_soft,
  * dqn_agent.py:389-399) with one tau per net: tau[NW], one_minus_tau[NW]
