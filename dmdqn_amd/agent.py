@@ -33,6 +33,11 @@ pbt_score() adds a step's reward to each replica's fitness; at a round
 pbt_select() ranks them, pbt_exchange() copies the best replicas' nets and Adam
 slots over the worst ones' in place and pbt_explore() perturbs the copied
 per-agent hyperparameters (the Trainer calls all four).
+
+Gradient clipping: with AgentConfig.global_clipnorm > 0 every learn runs as the
+split learn whose Adam launch first clips each agent's gradient by its global
+norm (Keras's Adam(global_clipnorm=...); include/dmdqn.h dmdqn_adam_agents_clip);
+grad_norm holds the norms before clipping and learn_metrics() reports them.
 """
 import ctypes as C
 import itertools
@@ -94,6 +99,8 @@ _lib.register({
     "dmdqn_learn_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p],
     "dmdqn_learn_grad_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_void_p],
     "dmdqn_adam_agents_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_void_p],
+    "dmdqn_adam_agents_clip": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_float,
+                               C.c_void_p, C.c_void_p],
     "dmdqn_learn_pair": [C.POINTER(CLearn), C.POINTER(CLearn), C.POINTER(CHParams),
                          C.POINTER(CHParams), C.c_void_p],
     "dmdqn_target_soft_update_hp": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -243,6 +250,22 @@ def check_tau(tau, allow_zero=True):
     if not (0.0 <= t <= 1.0) or (t == 0.0 and not allow_zero):
         raise ValueError(f"tau must be in {'[' if allow_zero else '('}0, 1], got {tau!r}")
     return t
+
+
+def check_clipnorm(clip):
+    """global_clipnorm as a float, or ValueError: finite and >= 0 (0 = no
+    clipping), and, when on, finite and > 0 as the float32 the kernel takes."""
+    try:
+        c = float(clip)
+    except (TypeError, ValueError):
+        raise ValueError(f"global_clipnorm must be a number, got {clip!r}") from None
+    if not (math.isfinite(c) and c >= 0.0):
+        raise ValueError(f"global_clipnorm must be finite and >= 0, got {clip!r}")
+    with np.errstate(over="ignore"):
+        c32 = np.float32(c)
+    if c > 0.0 and not (np.isfinite(c32) and c32 > 0.0):
+        raise ValueError(f"global_clipnorm = {clip!r} is not a positive finite float32")
+    return c
 
 
 SWEEP_KEYS = ("learning_rate", "gamma", "tau")
@@ -521,6 +544,16 @@ class AgentConfig:
     # a swept one (starting from the scalar when not swept).  None = off:
     # nothing is allocated or launched.
     pbt: Optional[dict] = None
+    # gradient clipping by global norm, Keras's Adam(global_clipnorm=...) (one
+    # keyword at dqn_agent.py:140, which the reference does not set): before
+    # the Adam step every agent's gradient g is scaled by about
+    # min(1, global_clipnorm / ||g||) over all of its parameters
+    # (include/dmdqn.h dmdqn_adam_agents_clip has the exact rule), and the norm
+    # is kept (BatchedDQN.grad_norm, learn_metrics).  0 = off: nothing is
+    # allocated or launched.  On, every learn runs as the split learn
+    # (set_split_learn) with the clipping Adam launch, alone (never paired):
+    # fp16 / bf16 independent networks on int8 replay rows.  Not a sweep key.
+    global_clipnorm: float = 0.0
 
     @classmethod
     def from_dict(cls, d):
@@ -534,7 +567,8 @@ class LearnToken:
     metrics buffers of the agent's rotations, the ring window, the Keras Adam
     constants and factors of this learn's step count, and whether it -- or the
     learn after it -- is a hard target sync."""
-    __slots__ = ("idx", "loss", "qstats", "adam", "factors", "sync", "next_sync", "start", "n")
+    __slots__ = ("idx", "loss", "qstats", "adam", "factors", "sync", "next_sync", "start", "n",
+                 "gnorm")
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -594,6 +628,14 @@ class BatchedDQN:
         if cfg.loss not in LOSSES:
             raise ValueError(f"loss must be one of {list(LOSSES)}")
         check_tau(cfg.tau)
+        # gradient clipping rides on the split learn: its limits are refused
+        # here, before anything is allocated
+        self.clipnorm = check_clipnorm(cfg.global_clipnorm)
+        if self.clipnorm > 0 and (cfg.precision not in H16_DTYPES or cfg.shared_params
+                                  or cfg.replay_rows != "int8"):
+            raise ValueError("global_clipnorm does not run with precision 'fp32', shared_params "
+                             "or float replay rows (replay_rows 'f32'): fp16 / bf16 independent "
+                             "networks on int8 replay rows are supported")
         if int(cfg.target_update_frequency) < 0:
             raise ValueError("target_update_frequency must be >= 0 (0 = never hard-sync)")
         if cfg.shared_params and (cfg.precision != "fp16" or H != 128):
@@ -689,6 +731,13 @@ class BatchedDQN:
         self._qstats_bufs = [torch.zeros((NA, 6), dtype=torch.float32, device=dev)
                              for _ in range(self.OUT_BUFS)]
         self.loss, self.qstats = self._loss_bufs[0], self._qstats_bufs[0]
+        # global_clipnorm: every agent's gradient norm before clipping, f32 [NA],
+        # rotating with the loss; None without clipping
+        self._gnorm_bufs = self.grad_norm = None
+        if self.clipnorm > 0:
+            self._gnorm_bufs = [torch.zeros(NA, dtype=torch.float32, device=dev)
+                                for _ in range(self.OUT_BUFS)]
+            self.grad_norm = self._gnorm_bufs[0]
         # rotating action buffers: a caller may still read step t's actions on
         # its stream while the trainer's side stream writes steps t+1 and t+2
         # (overlap "env": the side stream waits only for learn t, before which
@@ -751,6 +800,8 @@ class BatchedDQN:
             self.fitness = torch.zeros(num_envs, dtype=torch.float64, device=dev)
             self._pbt_rank = torch.empty(num_envs, dtype=torch.int32, device=dev)
             self._pbt_src = torch.empty(num_envs, dtype=torch.int32, device=dev)
+        if self.clipnorm > 0:  # the clipping Adam launch is the split learn's second one
+            self.set_split_learn(True)
 
     @property
     def swept(self):
@@ -772,6 +823,8 @@ class BatchedDQN:
                 self._split_grad = torch.empty((self.NA, self.P), dtype=torch.float32,
                                                device=self.device)
         else:
+            if self.clipnorm > 0:
+                raise ValueError("global_clipnorm runs as the split learn: it cannot be turned off")
             self._split_grad = None
 
     @property
@@ -890,6 +943,8 @@ class BatchedDQN:
                 and self.learn_step_counter % cfg.target_update_frequency == 0)
         k = self.learn_step_counter % self.OUT_BUFS
         self.loss = self._loss_bufs[k]
+        if self._gnorm_bufs is not None:
+            self.grad_norm = self._gnorm_bufs[k]
         qstats = None
         if collect_stats:
             # zeroed per agent range by learn_range, on the stream that launches
@@ -901,6 +956,7 @@ class BatchedDQN:
         self._last_tok = LearnToken(
             idx=self.idx, loss=self.loss, qstats=qstats, adam=(alpha, c1, c2, eps),
             factors=self._last_factors, sync=sync, start=self.ring.start, n=self.learn_step_counter,
+            gnorm=self.grad_norm,
             next_sync=cfg.target_update_frequency > 0 and nxt % cfg.target_update_frequency == 0)
         return self._last_tok
 
@@ -943,7 +999,13 @@ class BatchedDQN:
                     eps, LOSSES[cfg.loss], sl(qstats), sl(self.rn_out), sl(self.stamps))
             kw = dict(grad=sl(self._split_grad), xs=xs, xn=xn, tau=float(tau_f),
                       one_minus_tau=float(omt_f))
-            if self.swept:  # the range's slice of the per-agent arrays, like every tensor
+            if self.clipnorm > 0:  # the split learn with the clipping Adam launch
+                s, d = tok.factors
+                self._ops.learn_step_clip(*args, **kw, lr=sl(self.hp_lr), gamma_a=sl(self.hp_gamma),
+                                          tau_a=sl(self.hp_tau), one_minus_tau_a=sl(self.hp_omt),
+                                          adam_s=s, adam_d=d, clip=self.clipnorm,
+                                          gnorm=sl(tok.gnorm))
+            elif self.swept:  # the range's slice of the per-agent arrays, like every tensor
                 s, d = tok.factors
                 self._ops.learn_step_hp(*args, **kw, lr=sl(self.hp_lr), gamma_a=sl(self.hp_gamma),
                                         tau_a=sl(self.hp_tau), one_minus_tau_a=sl(self.hp_omt),
@@ -1046,7 +1108,10 @@ class BatchedDQN:
         mean over agents of q_values_mean / q_values_std (population std over
         each batch's 128x4 online Q values), the action histogram summed over
         agents, mean loss and epsilon, plus "n_step" (the config's: what the
-        loss and Q values were learned under).  by_variant: a list with one such record
+        loss and Q values were learned under).  With global_clipnorm also
+        "grad_norm_mean" / "grad_norm_max" (the agents' gradient norms before
+        clipping) and "clipped_frac" (the share of agents with norm > clip);
+        without it the record has no such keys.  by_variant: a list with one such record
         per sweep variant, reduced over the agents of the variant's replicas,
         plus "variant" (its index), its learning_rate / gamma / tau and "envs"
         (how many replicas run it; the scalars are None for a variant without
@@ -1061,11 +1126,18 @@ class BatchedDQN:
         std = (qs[:, 1] / n - mean * mean).clamp_min(0).sqrt()
         loss = self.loss.double()
 
+        gn = None if self.grad_norm is None else self.grad_norm.double()
+
         def record(sel):
-            return {"loss": float(loss[sel].mean()), "epsilon": float(self.epsilon),
-                    "n_step": self.n_step, "q_values_mean": float(mean[sel].mean()),
-                    "q_values_std": float(std[sel].mean()),
-                    "action_distribution": qs[sel, 2:6].sum(0).round().long().tolist()}
+            rec = {"loss": float(loss[sel].mean()), "epsilon": float(self.epsilon),
+                   "n_step": self.n_step, "q_values_mean": float(mean[sel].mean()),
+                   "q_values_std": float(std[sel].mean()),
+                   "action_distribution": qs[sel, 2:6].sum(0).round().long().tolist()}
+            if gn is not None:  # global_clipnorm: the norms before clipping
+                clip = float(np.float32(self.clipnorm))  # what the kernel compares with
+                rec.update(grad_norm_mean=float(gn[sel].mean()), grad_norm_max=float(gn[sel].max()),
+                           clipped_frac=float((gn[sel] > clip).double().mean()))
+            return rec
         if not by_variant:
             return record(slice(None))
         out = []
@@ -1078,6 +1150,8 @@ class BatchedDQN:
                 rec.update(loss=None, epsilon=float(self.epsilon), n_step=self.n_step,
                            q_values_mean=None,
                            q_values_std=None, action_distribution=[0] * N_ACTIONS)
+                if gn is not None:
+                    rec.update(grad_norm_mean=None, grad_norm_max=None, clipped_frac=None)
             out.append(rec)
         return out
 

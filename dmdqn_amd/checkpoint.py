@@ -45,7 +45,7 @@ _AGENT_TENSORS = ["params", "target", "adam_m", "adam_v", "np_state", "py_state"
 # derived state stale), so load() refuses it.
 _AGENT_FIXED = ["precision", "shared_params", "nn_layers", "replay_buffer_size", "batch_size",
                 "seed", "loss", "target_update_frequency", "count_env_steps", "replay_rows",
-                "ring_spare", "tau", "sweep", "n_step", "pbt"]
+                "ring_spare", "tau", "sweep", "n_step", "pbt", "global_clipnorm"]
 _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features", "cap_lane",
               "end_ms", "period_ms", "step_duration", "max_sim_time", "action_stride", "scenario",
               "actuated"]
@@ -57,9 +57,11 @@ _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features
 # n-step returns existed stored one-step transitions; the rings of another
 # n_step hold other returns and the learn another discount.  pbt: a checkpoint
 # saved before population-based training existed ran without it; the rounds'
-# schedule, perturbation and draws are part of the run)
+# schedule, perturbation and draws are part of the run.  global_clipnorm: a
+# checkpoint saved before gradient clipping existed ran without it; the Adam
+# slots of another value were built from other gradients)
 _DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2,
-             "tau": 0.0, "sweep": None, "n_step": 1, "pbt": None}
+             "tau": 0.0, "sweep": None, "n_step": 1, "pbt": None, "global_clipnorm": 0.0}
 _RING_TENSORS = ["s", "n", "a", "r", "d"]
 
 

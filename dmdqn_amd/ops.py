@@ -32,6 +32,7 @@ ENTRY_POINTS = {
     "dmdqn_target_sync": "target_sync", "dmdqn_target_soft_update": "target_soft_update",
     "dmdqn_learn_hp": "learn_step_hp", "dmdqn_learn_grad_hp": "learn_step_hp",
     "dmdqn_adam_agents_hp": "learn_step_hp", "dmdqn_learn_pair": "learn_pair",
+    "dmdqn_adam_agents_clip": "learn_step_clip",
     "dmdqn_target_soft_update_hp": "target_soft_update_hp",
     "dmdqn_q_argmax": "q_argmax",
     "dmdqn_q_argmax_shared": "q_argmax",

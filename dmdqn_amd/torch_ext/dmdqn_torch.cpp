@@ -476,6 +476,50 @@ void learn_step_hp(const Tensor &ring_s, const Tensor &ring_n, const Tensor &rin
     check(dmdqn_learn_hp(&a, &hp, stream_of(params)), "dmdqn_learn_hp");
 }
 
+// learn_step_hp as the split learn (grad required) with the gradient of every
+// agent clipped by its global norm before the Adam step (include/dmdqn.h
+// dmdqn_adam_agents_clip): clip > 0; gnorm f32 [NA] receives the norms before
+// clipping, or None.
+void learn_step_clip(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
+                     const Tensor &ring_d, const Tensor &ring_r, const Tensor &idx, Tensor &params,
+                     Tensor &adam_m, Tensor &adam_v, Tensor &target, const OptT &target_h,
+                     Tensor &loss, int64_t start, int64_t hidden, int64_t precision, bool sync,
+                     double gamma, double alpha, double c1, double c2, double eps,
+                     int64_t loss_kind, const OptT &qstats, const OptT &rn_out, const OptT &stamps,
+                     Tensor &grad, const OptT &xs, const OptT &xn, double tau,
+                     double one_minus_tau, const OptT &lr, const OptT &gamma_a, const OptT &tau_a,
+                     const OptT &one_minus_tau_a, double adam_s, double adam_d, double clip,
+                     const OptT &gnorm) {
+    const int64_t NA = loss.numel();
+    dmdqn_learn_args a = make_learn(ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m,
+                                    adam_v, target, target_h, loss, start, hidden, precision, sync,
+                                    gamma, alpha, c1, c2, eps, loss_kind, qstats, rn_out,
+                                    std::nullopt, stamps, NA, NA, xs, xn);
+    a.tau = (float)tau;
+    a.one_minus_tau = (float)one_minus_tau;
+    dmdqn_agent_hparams hp{};
+    hp.lr = optr<const float>(lr, at::kFloat, "lr", NA);
+    hp.gamma = optr<const float>(gamma_a, at::kFloat, "gamma_a", NA);
+    hp.tau = optr<const float>(tau_a, at::kFloat, "tau_a", NA);
+    hp.one_minus_tau = optr<const float>(one_minus_tau_a, at::kFloat, "one_minus_tau_a", NA);
+    TORCH_CHECK((hp.tau == nullptr) == (hp.one_minus_tau == nullptr),
+                "tau_a and one_minus_tau_a go together");
+    for (const OptT *t : {&lr, &gamma_a, &tau_a, &one_minus_tau_a, &gnorm})
+        TORCH_CHECK(!t->has_value() || (*t)->device() == params.device(),
+                    "per-agent hyperparameters and gnorm must be on the device of params");
+    hp.adam_s = (float)adam_s;
+    hp.adam_d = (float)adam_d;
+    auto gr = dptr<float>(grad, at::kFloat, "grad", NA * (int64_t)a.P);
+    auto gn = optr<float>(gnorm, at::kFloat, "gnorm", NA);
+    // (before the gradient launch: the Adam entry point would refuse it after)
+    TORCH_CHECK((float)clip > 0.0f && (float)clip <= std::numeric_limits<float>::max(),
+                "clip must be finite and > 0 as float32, got ", clip);
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    check(dmdqn_learn_grad_hp(&a, &hp, gr, stream_of(params)), "dmdqn_learn_grad_hp");
+    check(dmdqn_adam_agents_clip(&a, &hp, gr, (float)clip, gn, stream_of(params)),
+          "dmdqn_adam_agents_clip");
+}
+
 // Two consecutive learns of every agent in one launch (dmdqn_learn_pair): the
 // shared tensors once, then what a step fixes for each learn -- idx, loss,
 // start, adam = [alpha, c1, c2, eps], qstats, rn_out and, with per-agent
@@ -737,6 +781,13 @@ void learn_step_hp_meta(const Tensor &, const Tensor &, const Tensor &, const Te
                         double, double, double, int64_t, const OptT &, const OptT &, const OptT &,
                         const OptT &, const OptT &, const OptT &, double, double, const OptT &,
                         const OptT &, const OptT &, const OptT &, double, double) {}
+void learn_step_clip_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                          const Tensor &, const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &,
+                          const OptT &, Tensor &, int64_t, int64_t, int64_t, bool, double, double,
+                          double, double, double, int64_t, const OptT &, const OptT &, const OptT &,
+                          Tensor &, const OptT &, const OptT &, double, double, const OptT &,
+                          const OptT &, const OptT &, const OptT &, double, double, double,
+                          const OptT &) {}
 void learn_pair_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                      Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, const Tensor &,
                      const Tensor &, Tensor &, Tensor &, int64_t, int64_t, int64_t, int64_t, double,
@@ -827,6 +878,17 @@ TORCH_LIBRARY(dmdqn, m) {
           "Tensor? xs=None, Tensor? xn=None, float tau=0.0, float one_minus_tau=1.0, "
           "Tensor? lr=None, Tensor? gamma_a=None, Tensor? tau_a=None, "
           "Tensor? one_minus_tau_a=None, float adam_s=1.0, float adam_d=1.0) -> ()");
+    // learn_step_hp as the split learn with Keras's global_clipnorm on each agent's gradient
+    // (tf.keras.optimizers.Adam(global_clipnorm=...), one keyword at dqn_agent.py:140)
+    m.def("learn_step_clip(Tensor ring_s, Tensor ring_n, Tensor ring_a, Tensor ring_d, "
+          "Tensor ring_r, Tensor idx, Tensor(a!) params, Tensor(b!) adam_m, Tensor(c!) adam_v, "
+          "Tensor(d!) target, Tensor(e!)? target_h, Tensor(f!) loss, int start, int hidden, "
+          "int precision, bool sync, float gamma, float alpha, float c1, float c2, float eps, "
+          "int loss_kind, Tensor(g!)? qstats, Tensor(h!)? rn_out, Tensor(i!)? stamps, "
+          "Tensor(j!) grad, Tensor? xs=None, Tensor? xn=None, float tau=0.0, "
+          "float one_minus_tau=1.0, Tensor? lr=None, Tensor? gamma_a=None, Tensor? tau_a=None, "
+          "Tensor? one_minus_tau_a=None, float adam_s=1.0, float adam_d=1.0, *, float clip, "
+          "Tensor(k!)? gnorm=None) -> ()");
     // two consecutive DQNAgent.learn calls of every agent in one launch (dmdqn_learn_pair)
     m.def("learn_pair(Tensor ring_s, Tensor ring_n, Tensor ring_a, Tensor ring_d, Tensor ring_r, "
           "Tensor(a!) params, Tensor(b!) adam_m, Tensor(c!) adam_v, Tensor(d!) target, "
@@ -884,6 +946,7 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("env_step", &env_step);
     m.impl("learn_step", &learn_step);
     m.impl("learn_step_hp", &learn_step_hp);
+    m.impl("learn_step_clip", &learn_step_clip);
     m.impl("learn_pair", &learn_pair);
     m.impl("learn_shared_grad", &learn_shared_grad);
     m.impl("adam", &adam);
@@ -912,6 +975,7 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("env_step", &env_step_meta);
     m.impl("learn_step", &learn_step_meta);
     m.impl("learn_step_hp", &learn_step_hp_meta);
+    m.impl("learn_step_clip", &learn_step_clip_meta);
     m.impl("learn_pair", &learn_pair_meta);
     m.impl("learn_shared_grad", &learn_shared_grad_meta);
     m.impl("adam", &adam_meta);

@@ -267,6 +267,9 @@ class Trainer:
         also produce the metrics of dqn_agent.py:361-370 (agent.learn_metrics).
         Under the debug-bounds build (DMDQN_VARIANT=debug) every step ends with
         a device sync and the kernels' range checks."""
+        # the stream this step's work (its learn among it) is queued on or
+        # behind: sync_outputs() orders a read under another stream after it
+        self._step_stream = torch.cuda.current_stream(self.env.device)
         st = self._step(collect_stats)
         if self.agent.pbt is not None:
             self._pbt_after_step()
@@ -634,10 +637,19 @@ class Trainer:
         is LAUNCHED now (a kernel, on the learn stream of the step that began
         it; the current stream waits for it) -- so a loop that calls this, or
         reads last_loss, after every step never pairs.  With side_learn: the
-        current stream waits for the last step's side-stream learn.  A no-op
-        otherwise."""
+        current stream waits for the last step's side-stream learn.  Called
+        under another stream than the last step's: the current stream waits
+        for what that step queued (a learn launched within the step is not
+        otherwise ordered before a read there).  A no-op otherwise."""
         if getattr(self, "_pending", None) is not None:
             self._flush_pending()
+        last = getattr(self, "_step_stream", None)
+        if last is not None:
+            cur = torch.cuda.current_stream(self.env.device)
+            if cur != last:
+                ev = torch.cuda.Event()
+                ev.record(last)
+                cur.wait_event(ev)
         if getattr(self, "_side_pending", None) is not None:
             torch.cuda.current_stream(self.env.device).wait_event(self._side_pending)
 

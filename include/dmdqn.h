@@ -74,7 +74,10 @@ const char *dmdqn_last_error(void);
  * built at the replay store: the learn entry points and their structs are
  * unchanged and receive gamma^n for gamma.
  * dmdqn_learn_pair is new -- two consecutive learns of every agent in one
- * launch; dmdqn_learn and its structs are unchanged. */
+ * launch; dmdqn_learn and its structs are unchanged.
+ * dmdqn_adam_agents_clip is new -- the split learn's Adam launch with Keras's
+ * global-norm gradient clipping; dmdqn_adam_agents and its structs are
+ * unchanged. */
 int dmdqn_version(void);
 
 /* The digest of the sources this library was built from (16 hex chars:
@@ -585,6 +588,35 @@ int dmdqn_learn_grad_hp(const dmdqn_learn_args *args, const dmdqn_agent_hparams 
                         void *stream);
 int dmdqn_adam_agents_hp(const dmdqn_learn_args *args, const dmdqn_agent_hparams *hp,
                          const float *grad, void *stream);
+
+/* dmdqn_adam_agents_hp with each agent's gradient clipped by its global norm
+ * first: Keras 3's `global_clipnorm` (keras/src/optimizers/base_optimizer.py
+ * clip_by_global_norm / global_norm; tf.keras.optimizers.Adam(global_clipnorm=
+ * ...) is one keyword at dqn_agent.py:140, which the reference does not set).
+ * For one agent with gradient g[0..P) (what dmdqn_learn_grad wrote: f32 values
+ * exactly representable in 16 bits; the norm does not depend on the layout):
+ *     S     = sum_i g_i^2                        f64 (every square is exact)
+ *     norm  = fl32(sqrt(S))                      f64 sqrt, one rounding to f32
+ *     s_fin = fl32(clip * min(fl32(1 / norm), fl32(1 / clip)))
+ *     scale = fl32(s_fin + fl32(norm - norm))    NaN when norm is inf / NaN
+ *     g'_i  = fl32(g_i * scale)
+ * -- f32 operations rounded one by one, correctly rounded divides, no fma --
+ * and g' takes g's place in the Adam step of dmdqn_adam_agents_hp (alpha, c1,
+ * c2, eps, sync_target, tau and hp as there).  As in Keras: norm == 0 gives
+ * 1 / norm = inf and the min picks 1 / clip; an unclipped gradient is still
+ * multiplied by fl32(clip * fl32(1 / clip)), which is 1 for most clip values
+ * and 1 - 2^-24 for some; a non-finite gradient turns that agent's parameters
+ * and Adam slots to NaN and leaves every other agent alone.  Unlike Keras,
+ * which sums the squares in f32 per variable and then across variables, S is
+ * summed in f64, in one fixed order (no atomics: the same bits on every run).
+ * Keras's per-variable `clipnorm` and elementwise `clipvalue` are not offered.
+ * grad [NA][P] is read once and left unmodified; gnorm f32 [NA] receives the
+ * norm before clipping, or is NULL; hp may be NULL.  One workgroup per agent.
+ * Refused on the host (DMDQN_EINVAL, before any launch): everything
+ * dmdqn_adam_agents_hp refuses; clip not finite or <= 0; precision other than
+ * 1 / 2; P other than the 128-wide layout's (28,548). */
+int dmdqn_adam_agents_clip(const dmdqn_learn_args *args, const dmdqn_agent_hparams *hp,
+                           const float *grad, float clip, float *gnorm, void *stream);
 
 /* Two consecutive learns of every agent in ONE launch (two calls of
  * DQNAgent.learn, dqn_agent.py:328-380, with nothing of the agent's between

@@ -18,6 +18,7 @@ stage for all agents (dmdqn_amd.trainer.Trainer) -- the throughput path.
   python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 \
       --sweep learning_rate=1e-4,1e-3 --pbt interval=200   # the best replicas replace the worst
   python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 --n_step 3
+  python -m src.scripts.train --batched --envs 64 --grid 2x2 --episodes 1 --global_clipnorm 10
 """
 import argparse
 import json
@@ -98,15 +99,20 @@ def create_agents(tl_junctions, config=AGENT_CONFIG):
     return {j: DQNAgent(state_size=89, action_size=4, agent_id=j, config=config) for j in tl_junctions}
 
 
-def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG, n_step=1):
+def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG, n_step=1,
+                  global_clipnorm=0.0):
     """AGENT_CONFIG with the target-network rule of --tau /
     --target_update_frequency: soft updates (dqn_agent.py:372-373, 389-399) of
     rate tau after every learn, hard syncs every target_update_frequency learns
-    (0 = never; None = the config's); and --n_step: n-step returns built at the
-    replay store (AgentConfig.n_step; 1 = the reference's one-step transitions)."""
+    (0 = never; None = the config's); --n_step: n-step returns built at the
+    replay store (AgentConfig.n_step; 1 = the reference's one-step transitions);
+    and --global_clipnorm: gradient clipping by global norm
+    (AgentConfig.global_clipnorm; 0 = off, the reference's optimizer)."""
     config = dict(config)
     if n_step != 1:
         config["n_step"] = n_step
+    if global_clipnorm:
+        config["global_clipnorm"] = float(global_clipnorm)
     if tau:
         config["tau"] = float(tau)
     if target_update_frequency is not None:
@@ -208,7 +214,7 @@ def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenar
 def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, scenario=None,
                   shared=False, save_dir=None, resume=None, log_every=20, loss="mse",
                   actuated=False, tau=0.0, target_update_frequency=None, sweep=None, n_step=1,
-                  pbt=None):
+                  pbt=None, global_clipnorm=0.0):
     """E env replicas of the loop on the GPU.  The optional JSONL carries the
     reference's learn scalars (dqn_agent.py:361-370: loss, epsilon,
     q_values_mean / _std, action_distribution) and its per-step rewards with
@@ -218,7 +224,9 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     record then carries "variants" (per variant: its hyperparameters, replicas,
     total / smoothed total reward and learn scalars), the final line ranks the
     variants by smoothed total reward, and the exported Keras weights are those
-    of the best variant's first replica (the checkpoint holds them all).  pbt
+    of the best variant's first replica (the checkpoint holds them all).
+    global_clipnorm (AgentConfig.global_clipnorm): each record's learn scalars
+    then carry grad_norm_mean / grad_norm_max / clipped_frac too.  pbt
     (AgentConfig.pbt, parse_pbt): population-based training; the variants then
     dissolve, so a record written at a round carries that round's pbt_log
     entry, the final line a "pbt" block (rounds, copies, the best replica of
@@ -227,7 +235,8 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     best replica's."""
     from dmdqn_amd.agent import AgentConfig
     from dmdqn_amd.trainer import Trainer
-    cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency, n_step=n_step))
+    cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency, n_step=n_step,
+                                              global_clipnorm=global_clipnorm))
     cfg.precision, cfg.seed, cfg.shared_params, cfg.loss = precision, seed, shared, loss
     cfg.sweep, cfg.pbt = sweep, pbt
     tr = Trainer(EnvConfig(rows=rows, cols=cols, num_envs=envs, seed=seed, scenario=scenario,
@@ -391,18 +400,27 @@ def main():
                     help="with --pbt, repeatable: the factors a copied value of KEY "
                          "(learning_rate, gamma or tau) is multiplied by, one drawn per copy "
                          "(default learning_rate=0.8,1.25)")
+    ap.add_argument("--global_clipnorm", type=float, default=0.0, metavar="F",
+                    help="batched only: clip every agent's gradient to global norm F before the "
+                         "Adam step (Keras Adam(global_clipnorm=F)); 0 = off.  fp16 / bf16 "
+                         "independent nets; the metrics gain grad_norm_mean / _max / clipped_frac")
     args = ap.parse_args()
     try:
         sweep = parse_sweep(args.sweep)
         pbt = parse_pbt(args.pbt, args.pbt_perturb)
-        from dmdqn_amd.agent import check_n_step
+        from dmdqn_amd.agent import check_clipnorm, check_n_step
         check_n_step(args.n_step, AGENT_CONFIG["replay_buffer_size"])
+        check_clipnorm(args.global_clipnorm)
     except ValueError as e:
         ap.error(str(e))
     if sweep and not args.batched:
         ap.error("--sweep needs --batched")
     if pbt and not args.batched:
         ap.error("--pbt needs --batched")
+    if args.global_clipnorm and not args.batched:
+        ap.error("--global_clipnorm needs --batched (the drop-in DQNAgent keeps float rows)")
+    if args.global_clipnorm and (args.shared or args.precision == "fp32"):
+        ap.error("--global_clipnorm runs with --precision fp16 / bf16, not with --shared")
     logging.basicConfig(level=logging.INFO)
     rows, cols = (int(x) for x in args.grid.split("x"))
     scenario = args.scenario
@@ -414,7 +432,7 @@ def main():
         train_batched(args.episodes, rows, cols, args.envs, args.precision, args.seed, args.metrics,
                       scenario, args.shared, args.save_dir, args.resume, args.log_every, args.loss,
                       args.actuated, args.tau, args.target_update_frequency, sweep, args.n_step,
-                      pbt)
+                      pbt, args.global_clipnorm)
     else:
         train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir,
                      args.tau, args.target_update_frequency, args.n_step)
