@@ -70,6 +70,17 @@ class CNStep(C.Structure):
 SIGNATURES["dmdqn_replay_nstep_commit"] = [C.POINTER(CNStep), vp]
 
 
+class CProbe(C.Structure):
+    """include/dmdqn.h dmdqn_probe_args."""
+    _fields_ = [(n, C.c_int32) for n in ["NA", "cap", "start", "batch", "hidden", "precision",
+                                         "P"]] + [
+        (n, C.c_void_p) for n in ["ring_s", "idx", "params", "counts", "stats", "dead_mask"]]
+
+
+SIGNATURES["dmdqn_net_probe"] = [C.POINTER(CProbe), vp]
+SIGNATURES["dmdqn_layer_norms"] = [vp, vp, C.c_float, i32, i32, i32, i32, vp, vp]
+
+
 def register(sigs):
     """Add entry-point signatures (modules that define the ctypes structs call
     this); applied at once if the library is already loaded."""

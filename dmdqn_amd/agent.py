@@ -38,6 +38,13 @@ Gradient clipping: with AgentConfig.global_clipnorm > 0 every learn runs as the
 split learn whose Adam launch first clips each agent's gradient by its global
 norm (Keras's Adam(global_clipnorm=...); include/dmdqn.h dmdqn_adam_agents_clip);
 grad_norm holds the norms before clipping and learn_metrics() reports them.
+
+Network health probe: probe_health() runs every agent's online forward on its
+last batch and reduces it to dead / active ReLU units, non-finite
+pre-activations and per-variable weight norms and update-to-weight ratios
+(include/dmdqn.h dmdqn_net_probe, dmdqn_layer_norms); it only reads.  With
+AgentConfig.health_every = N a Trainer calls it after every N-th learn and
+learn_metrics() reports the last probe under "health".
 """
 import ctypes as C
 import itertools
@@ -267,6 +274,16 @@ def check_clipnorm(clip):
         raise ValueError(f"global_clipnorm = {clip!r} is not a positive finite float32")
     return c
 
+
+def check_health_every(n):
+    """health_every as an int, or ValueError: an integer >= 0 (0 = no probe)."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 0:
+        raise ValueError(f"health_every must be an integer >= 0, got {n!r}")
+    return int(n)
+
+
+# the Keras variables of one net, in get_weights order (dmdqn_layer_norms' columns)
+VARIABLES = ("W1", "b1", "W2", "b2", "W3", "b3")
 
 SWEEP_KEYS = ("learning_rate", "gamma", "tau")
 
@@ -554,6 +571,15 @@ class AgentConfig:
     # (set_split_learn) with the clipping Adam launch, alone (never paired):
     # fp16 / bf16 independent networks on int8 replay rows.  Not a sweep key.
     global_clipnorm: float = 0.0
+    # network health probe (docs/improvements.md item 2, "Tensorboard
+    # activation checks"): a Trainer probes every agent's online net after each
+    # health_every-th learn (BatchedDQN.probe_health: dead and active ReLU
+    # units, non-finite pre-activations, per-variable weight norms and
+    # update-to-weight ratios) and learn_metrics() gains a "health" block.  The
+    # probe only reads: training state is the same bits with and without it.
+    # 0 = off: nothing is allocated or launched.  fp16 / bf16 independent
+    # 128-wide networks on int8 replay rows.  Not a sweep key.
+    health_every: int = 0
 
     @classmethod
     def from_dict(cls, d):
@@ -636,6 +662,12 @@ class BatchedDQN:
             raise ValueError("global_clipnorm does not run with precision 'fp32', shared_params "
                              "or float replay rows (replay_rows 'f32'): fp16 / bf16 independent "
                              "networks on int8 replay rows are supported")
+        # the health probe runs the 16-bit learn's forward: the same limits,
+        # refused here as well
+        self.health_every = check_health_every(cfg.health_every)
+        if self.health_every > 0 and not self._probe_supported(cfg):
+            raise ValueError("health_every: " + self._PROBE_LIMITS)
+        self.health = None      # probe_health()'s outputs (device tensors), None before it ran
         if int(cfg.target_update_frequency) < 0:
             raise ValueError("target_update_frequency must be >= 0 (0 = never hard-sync)")
         if cfg.shared_params and (cfg.precision != "fp16" or H != 128):
@@ -830,6 +862,112 @@ class BatchedDQN:
     @property
     def split_learn(self):
         return self._split_grad is not None
+
+    # -------------------------------------------------------------- health probe
+    _PROBE_LIMITS = ("the network health probe does not run with precision 'fp32', "
+                     "shared_params, nn_layers other than [128, 128] or float replay rows "
+                     "(replay_rows 'f32'): fp16 / bf16 independent 128-wide networks on int8 "
+                     "replay rows are supported")
+
+    @staticmethod
+    def _probe_supported(cfg):
+        return (cfg.precision in H16_DTYPES and not cfg.shared_params
+                and list(cfg.nn_layers) == [128, 128] and cfg.replay_rows == "int8")
+
+    def probe_health(self, idx=None):
+        """Probe every agent's online net on the current stream (dmdqn_net_probe
+        and dmdqn_layer_norms; they only read): the forward of the batch at deque
+        positions idx [NA, 128] -- default: the last learn's draws, in that
+        learn's ring window -- reduced to counts / stats / dead_mask, and the
+        per-variable sums of squares of params (w2), of the Adam step m /
+        (sqrt(v) + eps) (u2) and, when the split learn's gradient buffer exists,
+        of the last gradient (g2, else None).  Fills and returns self.health, a
+        dict of device tensors: those, alpha f32 [NA] (the Adam factor of the
+        learn just done, per agent under a learning-rate sweep; 0 before the
+        first learn) and learn_step (int64 scalar); beside them "idx" and
+        "start", the index tensor and ring start the probe read.  The
+        update-to-weight ratio of a variable is alpha * sqrt(u2) / sqrt(w2)."""
+        if not self._probe_supported(self.cfg):
+            raise ValueError("probe_health: " + self._PROBE_LIMITS)
+        tok = self._last_tok
+        if idx is None:
+            if tok is None:
+                raise RuntimeError("probe_health: no learn has drawn a batch yet (pass idx)")
+            idx, start = tok.idx, tok.start
+        else:
+            start = self.ring.start
+        NA, dev = self.NA, self.device
+        h = self.health
+        if h is None:
+            h = self.health = {
+                "counts": torch.zeros((NA, K.PROBE_COUNTS), dtype=torch.int32, device=dev),
+                "stats": torch.zeros((NA, K.PROBE_STATS), dtype=torch.float64, device=dev),
+                "dead_mask": torch.zeros((NA, 2, 4), dtype=torch.int32, device=dev),
+                "w2": torch.zeros((NA, K.NORM_VARS), dtype=torch.float64, device=dev),
+                "u2": torch.zeros((NA, K.NORM_VARS), dtype=torch.float64, device=dev),
+                "g2": None,
+                "alpha": torch.zeros(NA, dtype=torch.float32, device=dev),
+                "learn_step": torch.zeros((), dtype=torch.int64, device=dev)}
+        K.net_probe(self.ring.s, idx, self.params, start, self.H, PRECISIONS[self.cfg.precision],
+                    h["counts"], h["stats"], h["dead_mask"])
+        eps = keras_adam_consts(1, self.cfg.learning_rate)[3]
+        K.layer_norms(self.params, self.H, out=h["w2"])
+        K.layer_norms(self.adam_m, self.H, y=self.adam_v, eps=eps, out=h["u2"])
+        if self._split_grad is not None:
+            if h["g2"] is None:
+                h["g2"] = torch.zeros((NA, K.NORM_VARS), dtype=torch.float64, device=dev)
+            K.layer_norms(self._split_grad, self.H, out=h["g2"])
+        else:
+            h["g2"] = None
+        if tok is None:
+            h["alpha"].zero_()
+        elif self.hp_lr is not None:
+            # fl32(fl32(lr * s) / d): the kernels' hp_alpha, two rounded f32 ops
+            s, d = tok.factors
+            torch.div(self.hp_lr * float(s), float(d), out=h["alpha"])
+        else:
+            h["alpha"].fill_(tok.adam[0])
+        h["learn_step"].fill_(self.learn_step_counter)
+        h["idx"], h["start"] = idx, int(start)  # what the probe read (not outputs)
+        return h
+
+    def health_metrics(self, sel=slice(None)):
+        """The "health" block of learn_metrics() from the last probe_health(),
+        reduced over the agents `sel`: per hidden layer dead_frac (mean over
+        agents of dead units / 128), dead_frac_max, active_frac, act_mean (the
+        mean activation) and preact_absmax; q_absmax; nonfinite_agents (agents
+        with a non-finite pre-activation or Q); per variable weight_norm (mean),
+        update_ratio (mean and max of alpha * sqrt(u2) / sqrt(w2) over the
+        agents whose variable is not all zero; None if there is none) and, with
+        the split learn's gradient, grad_layer_norm (mean).  Syncs."""
+        h = self.health
+        cnt = h["counts"][sel].double().cpu()
+        st = h["stats"][sel].cpu()
+        n = float(self.cfg.batch_size * self.H)
+        rec = {"learn_step": int(h["learn_step"]), "layers": [],
+               "q_absmax": float(st[:, 4].max()),
+               "nonfinite_agents": int((cnt[:, 4] > 0).sum())}
+        for layer in range(2):
+            dead = cnt[:, 2 * layer + 1] / self.H
+            rec["layers"].append({
+                "dead_frac": float(dead.mean()), "dead_frac_max": float(dead.max()),
+                "active_frac": float((cnt[:, 2 * layer] / n).mean()),
+                "act_mean": float((st[:, layer] / n).mean()),
+                "preact_absmax": float(st[:, 2 + layer].max())})
+        w = h["w2"][sel].sqrt().cpu()
+        step = h["alpha"][sel].double().cpu()[:, None] * h["u2"][sel].sqrt().cpu()
+        rec["weight_norm"] = {v: float(w[:, i].mean()) for i, v in enumerate(VARIABLES)}
+        ratio = {}
+        for i, v in enumerate(VARIABLES):
+            ok = w[:, i] > 0
+            r = step[ok, i] / w[ok, i]
+            ratio[v] = ({"mean": float(r.mean()), "max": float(r.max())} if bool(ok.any())
+                        else {"mean": None, "max": None})
+        rec["update_ratio"] = ratio
+        if h["g2"] is not None:
+            g = h["g2"][sel].sqrt().cpu()
+            rec["grad_layer_norm"] = {v: float(g[:, i].mean()) for i, v in enumerate(VARIABLES)}
+        return rec
 
     # -------------------------------------------------------------- act
     def current_epsilon(self):
@@ -1111,7 +1249,9 @@ class BatchedDQN:
         loss and Q values were learned under).  With global_clipnorm also
         "grad_norm_mean" / "grad_norm_max" (the agents' gradient norms before
         clipping) and "clipped_frac" (the share of agents with norm > clip);
-        without it the record has no such keys.  by_variant: a list with one such record
+        without it the record has no such keys.  With health_every on and after a
+        probe (probe_health) also "health", the block of health_metrics().
+        by_variant: a list with one such record
         per sweep variant, reduced over the agents of the variant's replicas,
         plus "variant" (its index), its learning_rate / gamma / tau and "envs"
         (how many replicas run it; the scalars are None for a variant without
@@ -1137,6 +1277,8 @@ class BatchedDQN:
                 clip = float(np.float32(self.clipnorm))  # what the kernel compares with
                 rec.update(grad_norm_mean=float(gn[sel].mean()), grad_norm_max=float(gn[sel].max()),
                            clipped_frac=float((gn[sel] > clip).double().mean()))
+            if self.health_every > 0 and self.health is not None:
+                rec["health"] = self.health_metrics(sel)
             return rec
         if not by_variant:
             return record(slice(None))
@@ -1152,6 +1294,8 @@ class BatchedDQN:
                            q_values_std=None, action_distribution=[0] * N_ACTIONS)
                 if gn is not None:
                     rec.update(grad_norm_mean=None, grad_norm_max=None, clipped_frac=None)
+                if self.health_every > 0 and self.health is not None:
+                    rec["health"] = None
             out.append(rec)
         return out
 

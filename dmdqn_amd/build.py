@@ -80,6 +80,8 @@ KERNEL_SOURCES = {
     "sim": ["sim.hip", "sim.hpp", "sim_rules.hpp", "observe.hpp", "common.hpp"],
     # population-based training (score / select / exchange): off the step's path
     "pbt": ["pbt.hip", "common.hpp"],
+    # the network health probe (forward reduced to counts; layer sums): off the step's path
+    "health": ["health.hip", "learn_img.hpp", "qnet_layout.hpp", "common.hpp"],
 }
 
 

@@ -59,9 +59,13 @@ _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features
 # saved before population-based training existed ran without it; the rounds'
 # schedule, perturbation and draws are part of the run.  global_clipnorm: a
 # checkpoint saved before gradient clipping existed ran without it; the Adam
-# slots of another value were built from other gradients)
+# slots of another value were built from other gradients.  health_every: a
+# checkpoint saved before the health probe existed ran without it; the probe
+# only reads and its outputs are not state, so the key is stored with the rest
+# of the config but a resume may set another value -- it is not in _AGENT_FIXED)
 _DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2,
-             "tau": 0.0, "sweep": None, "n_step": 1, "pbt": None, "global_clipnorm": 0.0}
+             "tau": 0.0, "sweep": None, "n_step": 1, "pbt": None, "global_clipnorm": 0.0,
+             "health_every": 0}
 _RING_TENSORS = ["s", "n", "a", "r", "d"]
 
 

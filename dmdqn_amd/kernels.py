@@ -258,3 +258,37 @@ def replay_sample(py_state, A, n, k=128, out=None, lds_budget=0):
         out = torch.empty((E * A, k), dtype=torch.int32, device=py_state.device)
     _ops().replay_sample(py_state, A, int(n), int(k), out, int(lds_budget))
     return out
+
+
+# ------------------------------------------------------------------ network health probe
+PROBE_COUNTS = 5  # include/dmdqn.h DMDQN_PROBE_COUNTS
+PROBE_STATS = 5   # DMDQN_PROBE_STATS
+NORM_VARS = 6     # dmdqn_layer_norms: W1, b1, W2, b2, W3, b3
+
+
+def net_probe(ring_s, idx, params, start, hidden, precision, counts=None, stats=None,
+              dead_mask=None):
+    """The online forward of every agent's batch reduced to health figures
+    (dmdqn_net_probe, current stream): counts int32 [NA, 5], stats f64 [NA, 5],
+    dead_mask int32 [NA, 2, 4] (uint32 words as bits).  Allocates the outputs
+    that are not given; returns (counts, stats, dead_mask)."""
+    NA, dev = params.shape[0], params.device
+    if counts is None:
+        counts = torch.empty((NA, PROBE_COUNTS), dtype=torch.int32, device=dev)
+    if stats is None:
+        stats = torch.empty((NA, PROBE_STATS), dtype=torch.float64, device=dev)
+    if dead_mask is None:
+        dead_mask = torch.empty((NA, 2, 4), dtype=torch.int32, device=dev)
+    _ops().net_probe(ring_s, idx, params, int(start), int(hidden), int(precision), counts, stats,
+                     dead_mask)
+    return counts, stats, dead_mask
+
+
+def layer_norms(x, hidden, y=None, eps=0.0, out=None):
+    """Per-variable sums of squares of x [NW, P] in Keras order W1, b1, W2, b2,
+    W3, b3 (dmdqn_layer_norms, current stream): of x itself, or with y (Adam v)
+    of x / (sqrt(y) + eps) as float32 operations.  Returns f64 [NW, 6]."""
+    if out is None:
+        out = torch.empty((x.shape[0], NORM_VARS), dtype=torch.float64, device=x.device)
+    _ops().layer_norms(x, y, float(eps), 0 if y is None else 1, int(hidden), out)
+    return out

@@ -38,6 +38,7 @@ ENTRY_POINTS = {
     "dmdqn_q_argmax_shared": "q_argmax",
     "dmdqn_pbt_score": "pbt_score", "dmdqn_pbt_select": "pbt_select",
     "dmdqn_pbt_exchange": "pbt_exchange",
+    "dmdqn_net_probe": "net_probe", "dmdqn_layer_norms": "layer_norms",
 }
 
 TORCH_LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"libdmdqn_torch{_lib._SUFFIX}.so")

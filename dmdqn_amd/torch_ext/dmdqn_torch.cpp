@@ -740,9 +740,62 @@ void pbt_exchange(const Tensor &src, int64_t A, Tensor &params, Tensor &target, 
           "dmdqn_pbt_exchange");
 }
 
+// ---------------------------------------------------------------- network health probe
+// The online forward of every agent's batch reduced to health figures
+// (include/dmdqn.h dmdqn_net_probe): counts int32 [NA, 5], stats f64 [NA, 5],
+// dead_mask int32 [NA, 2, 4] (the uint32 words as bits) or None.  Reads only.
+void net_probe(const Tensor &ring_s, const Tensor &idx, const Tensor &params, int64_t start,
+               int64_t hidden, int64_t precision, Tensor &counts, Tensor &stats,
+               const OptT &dead_mask) {
+    TORCH_CHECK(params.dim() == 2, "params must be [NA, P]");
+    const int64_t NA = params.size(0), P = params.size(1);
+    TORCH_CHECK(NA > 0 && idx.numel() % NA == 0, "idx must be [NA, batch]");
+    const int64_t B = idx.numel() / NA;
+    TORCH_CHECK(ring_s.numel() % (NA * DMDQN_ROW_BYTES) == 0 && ring_s.numel() > 0,
+                "ring_s must be [NA, cap, ", DMDQN_ROW_BYTES, "]");
+    const int64_t cap = ring_s.numel() / (NA * DMDQN_ROW_BYTES);
+    dmdqn_probe_args a{};
+    a.NA = int32_of(NA, "NA"); a.cap = int32_of(cap, "cap"); a.start = int32_of(start, "start");
+    a.batch = int32_of(B, "batch"); a.hidden = int32_of(hidden, "hidden");
+    a.precision = int32_of(precision, "precision"); a.P = int32_of(P, "P");
+    a.ring_s = dptr<const int8_t>(ring_s, at::kChar, "ring_s");
+    a.idx = dptr<const int32_t>(idx, at::kInt, "idx", NA * B);
+    a.params = dptr<const float>(params, at::kFloat, "params");
+    a.counts = dptr<int32_t>(counts, at::kInt, "counts", NA * DMDQN_PROBE_COUNTS);
+    a.stats = dptr<double>(stats, at::kDouble, "stats", NA * DMDQN_PROBE_STATS);
+    a.dead_mask = optr<uint32_t>(dead_mask, at::kInt, "dead_mask", NA * 2 * 4);
+    TORCH_CHECK(ring_s.device() == params.device() && idx.device() == params.device() &&
+                    counts.device() == params.device() && stats.device() == params.device(),
+                "every tensor must be on the device of params");
+    TORCH_CHECK(!dead_mask.has_value() || dead_mask->device() == params.device(),
+                "dead_mask must be on the device of params");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    check(dmdqn_net_probe(&a, stream_of(params)), "dmdqn_net_probe");
+}
+
+// Per-variable sums of squares of x [NW, P] (include/dmdqn.h dmdqn_layer_norms):
+// mode 0 of x, mode 1 of x / (sqrt(y) + eps); out f64 [NW, 6] in Keras order.
+void layer_norms(const Tensor &x, const OptT &y, double eps, int64_t mode, int64_t hidden,
+                 Tensor &out) {
+    TORCH_CHECK(x.dim() == 2, "x must be [NW, P]");
+    const int64_t NW = x.size(0), P = x.size(1);
+    auto xp = dptr<const float>(x, at::kFloat, "x");
+    auto yp = optr<const float>(y, at::kFloat, "y", NW * P);
+    auto o = dptr<double>(out, at::kDouble, "out", NW * 6);
+    TORCH_CHECK(out.device() == x.device() && (!y.has_value() || y->device() == x.device()),
+                "every tensor must be on the device of x");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+    check(dmdqn_layer_norms(xp, yp, (float)eps, int32_of(mode, "mode"), int32_of(NW, "NW"),
+                            int32_of(P, "P"), int32_of(hidden, "hidden"), o, stream_of(x)),
+          "dmdqn_layer_norms");
+}
+
 // Meta kernels: the ops only mutate their (a!) arguments, so tracing needs no
 // shape function beyond "nothing is returned".
 void pbt_score_meta(const Tensor &, Tensor &) {}
+void net_probe_meta(const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, int64_t,
+                    Tensor &, Tensor &, const OptT &) {}
+void layer_norms_meta(const Tensor &, const OptT &, double, int64_t, int64_t, Tensor &) {}
 void pbt_select_meta(const Tensor &, int64_t, Tensor &, Tensor &) {}
 void pbt_exchange_meta(const Tensor &, int64_t, Tensor &, Tensor &, Tensor &, Tensor &,
                        const OptT &) {}
@@ -929,6 +982,12 @@ TORCH_LIBRARY(dmdqn, m) {
     m.def("pbt_select(Tensor fitness, int n, Tensor(a!) rank, Tensor(b!) src) -> ()");
     m.def("pbt_exchange(Tensor src, int A, Tensor(a!) params, Tensor(b!) target, "
           "Tensor(c!) adam_m, Tensor(d!) adam_v, Tensor(e!)? target_h) -> ()");
+    // the network health probe (docs/improvements.md item 2, "Tensorboard activation checks";
+    // nothing in the reference's code computes it)
+    m.def("net_probe(Tensor ring_s, Tensor idx, Tensor params, int start, int hidden, "
+          "int precision, Tensor(a!) counts, Tensor(b!) stats, Tensor(c!)? dead_mask=None) -> ()");
+    m.def("layer_norms(Tensor x, Tensor? y, float eps, int mode, int hidden, "
+          "Tensor(a!) out) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
@@ -958,6 +1017,8 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("pbt_score", &pbt_score);
     m.impl("pbt_select", &pbt_select);
     m.impl("pbt_exchange", &pbt_exchange);
+    m.impl("net_probe", &net_probe);
+    m.impl("layer_norms", &layer_norms);
 }
 
 TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
@@ -987,4 +1048,6 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("pbt_score", &pbt_score_meta);
     m.impl("pbt_select", &pbt_select_meta);
     m.impl("pbt_exchange", &pbt_exchange_meta);
+    m.impl("net_probe", &net_probe_meta);
+    m.impl("layer_norms", &layer_norms_meta);
 }

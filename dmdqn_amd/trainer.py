@@ -271,11 +271,39 @@ class Trainer:
         # behind: sync_outputs() orders a read under another stream after it
         self._step_stream = torch.cuda.current_stream(self.env.device)
         st = self._step(collect_stats)
+        n = self.agent.health_every
+        if n > 0 and st.loss_launched and self.agent.learn_step_counter % n == 0:
+            self._probe_health()
         if self.agent.pbt is not None:
             self._pbt_after_step()
         if self._debug:
             _lib.debug_check()
         return st
+
+    def _probe_health(self):
+        """The network health probe (AgentConfig.health_every) behind the learn
+        this step began, on the step's stream: sync_outputs() first launches a
+        held-back paired learn and waits for a side learn, so the probe sees the
+        nets and Adam slots that learn left; it reads them, that learn's index
+        buffer and its ring window, and writes only agent.health.
+        Under the "env" schedule the side stream runs ahead of the learn stream,
+        and this is safe: the stores of the next ring_spare calls land outside
+        the window the probe reads (kernels.ReplayRing), and the first store
+        that lands inside it -- like the first reuse of this call's index
+        buffer, ring_spare + 2 calls on -- waits for a mark of this call or a
+        later one.  Later marks are recorded on the learn stream behind the
+        probe; this call's own mark, if it has one, was recorded behind the
+        learn and ahead of the probe, so it is recorded again here (no wait on
+        it has been issued yet: the side stream waits for marks of calls two or
+        more back)."""
+        self.sync_outputs()
+        self.agent.probe_health()
+        if self.overlap == "env" and self._marks and self._marks[-1][0] == self._calls - 1:
+            self._marks[-1][1].record(torch.cuda.current_stream(self.env.device))
+        if self.side_learn:
+            # the next side learn writes its agents' nets on the side stream,
+            # which nothing else orders behind this stream's reads of them
+            self.side.wait_stream(torch.cuda.current_stream(self.env.device))
 
     def _pbt_after_step(self):
         """Population-based training, on the caller's stream: the step's reward

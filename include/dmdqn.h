@@ -755,6 +755,61 @@ int dmdqn_pbt_exchange(const int32_t *src, int E, int A, int P, int Ph, float *p
                        float *target, float *adam_m, float *adam_v, uint16_t *target_h,
                        void *stream);
 
+/* ------------------------------------------------------------------ network health probe
+ * The reference's to-do list asks for it (docs/improvements.md item 2,
+ * "Tensorboard activation checks (prevent explosion, vanishing)"); nothing in
+ * its code computes it.  Both entry points only read the training state. */
+
+/* The online forward of each agent's batch, reduced to health figures.  The
+ * forward is the 16-bit learn's on the batch's S rows (dmdqn_learn, precision
+ * 1 / 2): inputs, weights and biases cast to f16 / bf16, f32 sums,
+ *     z = h16(h16(acc) + b),   h = z > 0 ? z : 0   (a NaN z gives h = 0),
+ * Q the 16-bit z3.  Row p of the batch is ring slot (start + idx[p]) % cap.
+ * counts int32 [NA][5]:
+ *   [0] the (row, unit) pairs with h1 > 0;  [1] the layer-1 units with h1 == 0
+ *   on all 128 rows (dead on this batch);  [2], [3] the same for layer 2;
+ *   [4] the entries of z1, z2 and q that are not finite.
+ * stats f64 [NA][5]:
+ *   [0], [1] the sum of h1 / of h2 over the batch (16-bit values widened
+ *   exactly; summed per lane in row-tile order, across the wave by a butterfly,
+ *   then over the waves in order: no atomics, the same bits on every run);
+ *   [2], [3], [4] the largest |z1|, |z2|, |q| over the finite entries (0 if
+ *   there is none).
+ * dead_mask uint32 [NA][2][4] or NULL: bit u % 32 of word u / 32 of layer l is
+ * set when unit u of hidden layer l is dead on this batch.
+ * One 512-thread workgroup per agent.  Refused on the host (DMDQN_EINVAL,
+ * before any launch): null pointers (dead_mask excepted), NA <= 0, cap <= 0,
+ * batch != 128, hidden != 128, P != 28,548, precision other than 1 / 2, start
+ * outside [0, cap). */
+#define DMDQN_PROBE_COUNTS 5
+#define DMDQN_PROBE_STATS 5
+typedef struct dmdqn_probe_args {
+    int32_t NA, cap, start, batch, hidden, precision, P; /* as dmdqn_learn_args */
+    const int8_t *ring_s;   /* [NA][cap][DMDQN_ROW_BYTES], int8 rows */
+    const int32_t *idx;     /* [NA][batch] deque positions */
+    const float *params;    /* [NA][P] online nets, device layout */
+    int32_t *counts;        /* [NA][DMDQN_PROBE_COUNTS] out */
+    double *stats;          /* [NA][DMDQN_PROBE_STATS] out */
+    uint32_t *dead_mask;    /* NULL or [NA][2][4] out */
+} dmdqn_probe_args;
+int dmdqn_net_probe(const dmdqn_probe_args *args, void *stream);
+
+/* Per-variable sums of squares of a per-net f32 array x [NW][P] in the device
+ * layout: out f64 [NW][6] in Keras variable order W1, b1, W2, b2, W3, b3 (the
+ * layout's contiguous segments: W1 is the tiled block plus the feature-88
+ * column).  mode 0: sum of x^2.  mode 1: sum of u^2 with
+ *     u = fl32(x / fl32(fl32(sqrtf(y)) + eps)),   x = Adam m, y = Adam v
+ * (f32 operations rounded one by one, correctly rounded sqrt and divide), the
+ * Adam step without its factor: the update-to-weight ratio of a variable is
+ * alpha * sqrt(out1) / sqrt(out0).  Squares and sums are f64 (every square of
+ * an f32 is exact), each segment summed per thread in index order, across the
+ * wave by a butterfly, then over the waves in order: no atomics.  One
+ * workgroup per net.  hidden 64 or 128; NW = 1 for the shared net.  Refused on
+ * the host (DMDQN_EINVAL): x or out NULL, y NULL in mode 1, a mode other than
+ * 0 / 1, NW <= 0, hidden other than 64 / 128, P other than that width's. */
+int dmdqn_layer_norms(const float *x, const float *y, float eps, int mode, int NW, int P,
+                      int hidden, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

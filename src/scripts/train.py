@@ -100,15 +100,19 @@ def create_agents(tl_junctions, config=AGENT_CONFIG):
 
 
 def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG, n_step=1,
-                  global_clipnorm=0.0):
+                  global_clipnorm=0.0, health_every=0):
     """AGENT_CONFIG with the target-network rule of --tau /
     --target_update_frequency: soft updates (dqn_agent.py:372-373, 389-399) of
     rate tau after every learn, hard syncs every target_update_frequency learns
     (0 = never; None = the config's); --n_step: n-step returns built at the
     replay store (AgentConfig.n_step; 1 = the reference's one-step transitions);
     and --global_clipnorm: gradient clipping by global norm
-    (AgentConfig.global_clipnorm; 0 = off, the reference's optimizer)."""
+    (AgentConfig.global_clipnorm; 0 = off, the reference's optimizer); and
+    --health_every: the network health probe after every N-th learn
+    (AgentConfig.health_every; 0 = off)."""
     config = dict(config)
+    if health_every:
+        config["health_every"] = int(health_every)
     if n_step != 1:
         config["n_step"] = n_step
     if global_clipnorm:
@@ -214,7 +218,7 @@ def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenar
 def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, scenario=None,
                   shared=False, save_dir=None, resume=None, log_every=20, loss="mse",
                   actuated=False, tau=0.0, target_update_frequency=None, sweep=None, n_step=1,
-                  pbt=None, global_clipnorm=0.0):
+                  pbt=None, global_clipnorm=0.0, health_every=0):
     """E env replicas of the loop on the GPU.  The optional JSONL carries the
     reference's learn scalars (dqn_agent.py:361-370: loss, epsilon,
     q_values_mean / _std, action_distribution) and its per-step rewards with
@@ -226,7 +230,10 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     variants by smoothed total reward, and the exported Keras weights are those
     of the best variant's first replica (the checkpoint holds them all).
     global_clipnorm (AgentConfig.global_clipnorm): each record's learn scalars
-    then carry grad_norm_mean / grad_norm_max / clipped_frac too.  pbt
+    then carry grad_norm_mean / grad_norm_max / clipped_frac too.  health_every
+    (AgentConfig.health_every): once a probe has run, each record's learn
+    scalars (per variant too) carry the "health" block of the last probe, and
+    the final line's variants their dead_frac and update_ratio.  pbt
     (AgentConfig.pbt, parse_pbt): population-based training; the variants then
     dissolve, so a record written at a round carries that round's pbt_log
     entry, the final line a "pbt" block (rounds, copies, the best replica of
@@ -236,7 +243,8 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     from dmdqn_amd.agent import AgentConfig
     from dmdqn_amd.trainer import Trainer
     cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency, n_step=n_step,
-                                              global_clipnorm=global_clipnorm))
+                                              global_clipnorm=global_clipnorm,
+                                              health_every=health_every))
     cfg.precision, cfg.seed, cfg.shared_params, cfg.loss = precision, seed, shared, loss
     cfg.sweep, cfg.pbt = sweep, pbt
     tr = Trainer(EnvConfig(rows=rows, cols=cols, num_envs=envs, seed=seed, scenario=scenario,
@@ -294,6 +302,12 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
                                           smooth_variant.get_values() or [None] * len(variants))
         if final["variants"]:
             best_env = final["variants"][0]["first_env"]
+        if health_every and tr.agent.health is not None:  # the last probe, per variant
+            tr.sync_outputs()
+            for row in final["variants"]:
+                h = tr.agent.health_metrics(tr.agent._variant_of_agent == row["variant"])
+                row["dead_frac"] = [layer["dead_frac"] for layer in h["layers"]]
+                row["update_ratio"] = {k: v["mean"] for k, v in h["update_ratio"].items()}
     if pbt:
         ag = tr.agent
         if tr.pbt_log:
@@ -404,11 +418,17 @@ def main():
                     help="batched only: clip every agent's gradient to global norm F before the "
                          "Adam step (Keras Adam(global_clipnorm=F)); 0 = off.  fp16 / bf16 "
                          "independent nets; the metrics gain grad_norm_mean / _max / clipped_frac")
+    ap.add_argument("--health_every", type=int, default=0, metavar="N",
+                    help="batched only: probe every agent's network after each N-th learn (dead "
+                         "and active ReLU units, non-finite activations, weight norms, "
+                         "update-to-weight ratios); the metrics gain a \"health\" block.  0 = "
+                         "off.  fp16 / bf16 independent nets")
     args = ap.parse_args()
     try:
         sweep = parse_sweep(args.sweep)
         pbt = parse_pbt(args.pbt, args.pbt_perturb)
-        from dmdqn_amd.agent import check_clipnorm, check_n_step
+        from dmdqn_amd.agent import check_clipnorm, check_health_every, check_n_step
+        check_health_every(args.health_every)
         check_n_step(args.n_step, AGENT_CONFIG["replay_buffer_size"])
         check_clipnorm(args.global_clipnorm)
     except ValueError as e:
@@ -421,6 +441,10 @@ def main():
         ap.error("--global_clipnorm needs --batched (the drop-in DQNAgent keeps float rows)")
     if args.global_clipnorm and (args.shared or args.precision == "fp32"):
         ap.error("--global_clipnorm runs with --precision fp16 / bf16, not with --shared")
+    if args.health_every and not args.batched:
+        ap.error("--health_every needs --batched")
+    if args.health_every and (args.shared or args.precision == "fp32"):
+        ap.error("--health_every runs with --precision fp16 / bf16, not with --shared")
     logging.basicConfig(level=logging.INFO)
     rows, cols = (int(x) for x in args.grid.split("x"))
     scenario = args.scenario
@@ -432,7 +456,7 @@ def main():
         train_batched(args.episodes, rows, cols, args.envs, args.precision, args.seed, args.metrics,
                       scenario, args.shared, args.save_dir, args.resume, args.log_every, args.loss,
                       args.actuated, args.tau, args.target_update_frequency, sweep, args.n_step,
-                      pbt, args.global_clipnorm)
+                      pbt, args.global_clipnorm, args.health_every)
     else:
         train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir,
                      args.tau, args.target_update_frequency, args.n_step)
