@@ -85,7 +85,9 @@ __global__ void __launch_bounds__(64) k_act(uint32_t *np_state, int A, double ep
     const int e = blockIdx.x;
     uint32_t *g = np_state + (size_t)e * DMDQN_MT_WORDS;
     const int per = draw_rand ? 3 : 1, mti0 = (int)g[MT_N];
-    if (act_fast_ok(mti0, A, per, eps, rng, mask, draw_rand)) {  // one wave: reads before the write
+    // rng == 0 (one action): numpy's randint(0, 1) draws no word, so the draw
+    // count is not `per`: the general path below takes it
+    if (rng != 0u && act_fast_ok(mti0, A, per, eps, rng, mask, draw_rand)) {  // one wave: reads before the write
         for (int j = threadIdx.x; j < A; j += 64)
             actions[(size_t)e * A + j] = act_fast(g, mti0, j, per, mask);
         if (threadIdx.x == 0) g[MT_N] = (uint32_t)(mti0 + A * per);
@@ -96,8 +98,10 @@ __global__ void __launch_bounds__(64) k_act(uint32_t *np_state, int A, double ep
         const double r = draw_rand ? np_double(w) : 0.0;
         int32_t a;
         if (r < eps) {  // dqn_agent.py:263-265
-            uint32_t v;
-            do { v = w.next() & mask; } while (v > rng);
+            uint32_t v = 0u;
+            if (rng != 0u) {  // randint(0, 1) is 0 and leaves the stream where it is
+                do { v = w.next() & mask; } while (v > rng);
+            }
             a = (int32_t)v;
         } else {
             a = greedy[(size_t)e * A + j];

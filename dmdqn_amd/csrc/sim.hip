@@ -1641,7 +1641,11 @@ extern "C" int dmdqn_env_step(const dmdqn_sim *sim, const dmdqn_idm *idm, const 
                               int32_t *phase, int32_t *tspent, uint8_t *done, void *stream) {
     DMDQN_REQUIRE(F, "dmdqn_env_step: null fuse");
     DMDQN_REQUIRE(sim && sim->R * sim->C <= 100, "dmdqn_env_step: at most 100 junctions");
-    DMDQN_REQUIRE(F->np_state && F->actions && F->n_actions >= 1, "dmdqn_env_step: act arguments");
+    DMDQN_REQUIRE(F->np_state && F->actions, "dmdqn_env_step: act arguments");
+    // one action: numpy's randint(0, 1) draws no word, which the fixed three
+    // words per agent of the block's act would not follow (dmdqn_act does)
+    DMDQN_REQUIRE(F->n_actions >= 2, "dmdqn_env_step: n_actions must be >= 2 (got %d)",
+                  (int)F->n_actions);
     DMDQN_REQUIRE(F->greedy || F->eps >= 1.0, "dmdqn_env_step: greedy actions required when eps < 1");
     DMDQN_REQUIRE(F->mode == 0 || F->mode == 1, "dmdqn_env_step: mode must be 0 or 1");
     DMDQN_REQUIRE(F->local && F->obs && F->prev_local && F->reward, "dmdqn_env_step: observe arrays");

@@ -8,6 +8,7 @@ torch's current stream.
 """
 import time
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -34,8 +35,25 @@ def _check(t, dtype, shape=None, name="tensor"):
 # ------------------------------------------------------------------ streams
 def seed_streams(seeds, kind, device="cuda"):
     """Device MT19937 streams, one per env.  kind 'np' (numpy RandomState.seed)
-    or 'py' (CPython random.seed).  Returns uint32-as-int32 [E, 625]."""
-    seeds = torch.as_tensor(seeds, dtype=torch.int64).to(device).contiguous()
+    or 'py' (CPython random.seed).  Returns uint32-as-int32 [E, 625].
+
+    The seeds are checked on the host before anything is launched: a negative
+    seed of either kind raises ValueError (CPython would seed with abs(seed),
+    numpy refuses it; the kernels read the two's complement as a huge key),
+    and so does an np seed >= 2**32 (numpy: "Seed must be between 0 and
+    2**32 - 1"; the kernel would keep its low word) or a py seed >= 2**63
+    (beyond the int64 the kernels are handed)."""
+    if kind not in ("np", "py"):
+        raise ValueError("kind must be 'np' or 'py'")
+    if isinstance(seeds, torch.Tensor):
+        host = seeds.detach().cpu().reshape(-1).tolist()
+    else:
+        host = [int(s) for s in np.asarray(seeds, dtype=object).reshape(-1)]
+    top = 2 ** 32 if kind == "np" else 2 ** 63
+    for s in host:
+        if not 0 <= s < top:
+            raise ValueError(f"{kind} seed {s} is outside [0, 2**{32 if kind == 'np' else 63} - 1]")
+    seeds = torch.as_tensor(host, dtype=torch.int64).reshape(-1).to(device).contiguous()
     E = seeds.numel()
     st = torch.empty((E, MT_WORDS), dtype=torch.int32, device=device)
     _ops().mt_seed(st, seeds, "np" if kind == "np" else "py")

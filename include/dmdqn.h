@@ -173,7 +173,11 @@ int dmdqn_stream_probe(void *dst, const void *src, size_t n_bytes, int mode, voi
  *       np.random stream drawn at src/agents/dqn_agent.py:263-265.
  *  _py: CPython random.seed(int) (init_by_array of the 32-bit words); replaces
  *       the global `random` stream drawn at src/agents/dqn_agent.py:63.
- * state: uint32 [E][DMDQN_MT_WORDS];  seeds: uint64 [E] (device memory). */
+ * state: uint32 [E][DMDQN_MT_WORDS];  seeds: uint64 [E] (device memory).
+ * The kernels take the words as they are -- _np keeps the low 32 bits, _py
+ * keys with one or two 32-bit words: the caller refuses what the generators
+ * themselves refuse or reinterpret (kernels.seed_streams raises ValueError for
+ * a negative seed and for an np seed >= 2^32). */
 int dmdqn_mt_seed_np(uint32_t *state, const uint64_t *seeds, int E, void *stream);
 int dmdqn_mt_seed_py(uint32_t *state, const uint64_t *seeds, int E, void *stream);
 
@@ -185,7 +189,10 @@ int dmdqn_mt_draw_u32(uint32_t *state, int E, int count, uint32_t *out, void *st
  * agents of all envs: per env, agents in junction order draw rand() then, if
  * rand() < eps, randint(0, n_actions) from the env's numpy stream; otherwise
  * take greedy[e*A+j] (argmax of the online Q, see dmdqn_q_argmax).
- * greedy may be NULL only when eps >= 1.  actions: int32 [E*A]. */
+ * greedy may be NULL only when eps >= 1.  actions: int32 [E*A].
+ * n_actions >= 1.  With n_actions == 1 randint(0, 1) is 0 and draws no word,
+ * as numpy's: dmdqn_act consumes the two words of rand() per agent,
+ * dmdqn_act_uniform none. */
 int dmdqn_act(uint32_t *np_state, int E, int A, double eps, int n_actions,
               const int32_t *greedy, int32_t *actions, void *stream);
 
@@ -393,7 +400,10 @@ int dmdqn_sim_step(const dmdqn_sim *sim, const dmdqn_idm *idm, const int32_t *ac
  * passing them through HBM (three fewer launches per step). */
 typedef struct dmdqn_env_fuse {
     /* act (dmdqn_act): np_state [E][DMDQN_MT_WORDS]; greedy [E*A] (NULL when
-     * eps >= 1); actions [E*A] out */
+     * eps >= 1); actions [E*A] out.  n_actions >= 2: a single action is
+     * refused (DMDQN_EINVAL, nothing launched, the stream untouched) -- the
+     * block's act counts three words per agent where numpy's randint(0, 1)
+     * draws none; dmdqn_act handles that case */
     uint32_t *np_state;
     const int32_t *greedy;
     int32_t *actions;
