@@ -81,6 +81,17 @@ SIGNATURES["dmdqn_net_probe"] = [C.POINTER(CProbe), vp]
 SIGNATURES["dmdqn_layer_norms"] = [vp, vp, C.c_float, i32, i32, i32, i32, vp, vp]
 
 
+class CRedo(C.Structure):
+    """include/dmdqn.h dmdqn_redo_args."""
+    _fields_ = [(n, C.c_int32) for n in ["NA", "P", "hidden", "agent0", "patience"]] + [
+        ("round", C.c_uint32), ("seed", C.c_uint64), ("lim1", C.c_float), ("lim2", C.c_float)] + [
+        (n, C.c_void_p) for n in ["dead_mask", "streak", "params", "adam_m", "adam_v", "recycled",
+                                  "n_recycled"]]
+
+
+SIGNATURES["dmdqn_redo"] = [C.POINTER(CRedo), vp]
+
+
 def register(sigs):
     """Add entry-point signatures (modules that define the ctypes structs call
     this); applied at once if the library is already loaded."""

@@ -45,6 +45,12 @@ pre-activations and per-variable weight norms and update-to-weight ratios
 (include/dmdqn.h dmdqn_net_probe, dmdqn_layer_norms); it only reads.  With
 AgentConfig.health_every = N a Trainer calls it after every N-th learn and
 learn_metrics() reports the last probe under "health".
+
+Dead-unit recycling: redo() runs that probe and gives every hidden unit that
+was dead on redo_patience probes in a row fresh incoming weights, zero outgoing
+weights and zero Adam moments (ReDo; include/dmdqn.h dmdqn_redo).  With
+AgentConfig.redo_every = N a Trainer calls it after every N-th learn and
+learn_metrics() reports the rounds under "redo".
 """
 import ctypes as C
 import itertools
@@ -280,6 +286,18 @@ def check_health_every(n):
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 0:
         raise ValueError(f"health_every must be an integer >= 0, got {n!r}")
     return int(n)
+
+
+def check_redo(every, patience):
+    """(redo_every, redo_patience) as ints, or ValueError: redo_every an integer
+    >= 0 (0 = no recycling), redo_patience an integer in 1..255 (the streak is
+    one byte per unit)."""
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or int(every) < 0:
+        raise ValueError(f"redo_every must be an integer >= 0, got {every!r}")
+    if (isinstance(patience, bool) or not isinstance(patience, (int, np.integer))
+            or not 1 <= int(patience) <= 255):
+        raise ValueError(f"redo_patience must be an integer in 1..255, got {patience!r}")
+    return int(every), int(patience)
 
 
 # the Keras variables of one net, in get_weights order (dmdqn_layer_norms' columns)
@@ -580,6 +598,18 @@ class AgentConfig:
     # 0 = off: nothing is allocated or launched.  fp16 / bf16 independent
     # 128-wide networks on int8 replay rows.  Not a sweep key.
     health_every: int = 0
+    # dead-unit recycling, ReDo with tau = 0 (Sokar et al. 2023; also
+    # docs/improvements.md item 3, "improve weight inits"): after each
+    # redo_every-th learn a Trainer probes every agent's online net
+    # (BatchedDQN.redo) and a hidden unit that was dead on redo_patience such
+    # probes in a row gets fresh HeUniform incoming weights, zero outgoing
+    # weights and zero Adam moments (include/dmdqn.h dmdqn_redo): the network's
+    # function on the probed batch is unchanged.  learn_metrics() gains a
+    # "redo" block.  0 = off: nothing is allocated or launched.  The probe's
+    # limits: fp16 / bf16 independent 128-wide networks on int8 replay rows.
+    # Not sweep keys.
+    redo_every: int = 0
+    redo_patience: int = 1
 
     @classmethod
     def from_dict(cls, d):
@@ -668,6 +698,15 @@ class BatchedDQN:
         if self.health_every > 0 and not self._probe_supported(cfg):
             raise ValueError("health_every: " + self._PROBE_LIMITS)
         self.health = None      # probe_health()'s outputs (device tensors), None before it ran
+        # dead-unit recycling acts on the probe's dead mask: the probe's limits
+        self.redo_every, self.redo_patience = check_redo(cfg.redo_every, cfg.redo_patience)
+        if self.redo_every > 0 and not self._probe_supported(cfg):
+            raise ValueError("redo_every: " + self._PROBE_LIMITS)
+        # redo()'s state (device tensors; allocated with redo_every > 0 or by the
+        # first call): every unit's streak of dead probes, the last call's fired
+        # mask and counts, the running totals; and the number of calls
+        self.redo_streak = self.redo_last = self.redo_total = None
+        self.redo_rounds = 0
         if int(cfg.target_update_frequency) < 0:
             raise ValueError("target_update_frequency must be >= 0 (0 = never hard-sync)")
         if cfg.shared_params and (cfg.precision != "fp16" or H != 128):
@@ -834,6 +873,8 @@ class BatchedDQN:
             self._pbt_src = torch.empty(num_envs, dtype=torch.int32, device=dev)
         if self.clipnorm > 0:  # the clipping Adam launch is the split learn's second one
             self.set_split_learn(True)
+        if self.redo_every > 0:
+            self._redo_alloc()
 
     @property
     def swept(self):
@@ -968,6 +1009,55 @@ class BatchedDQN:
             g = h["g2"][sel].sqrt().cpu()
             rec["grad_layer_norm"] = {v: float(g[:, i].mean()) for i, v in enumerate(VARIABLES)}
         return rec
+
+    # -------------------------------------------------------------- dead-unit recycling
+    def _redo_alloc(self):
+        if self.redo_streak is None:
+            NA, dev = self.NA, self.device
+            self.redo_streak = torch.zeros((NA, 2, self.H), dtype=torch.uint8, device=dev)
+            self.redo_last = {
+                "recycled": torch.zeros((NA, 2, 4), dtype=torch.int32, device=dev),
+                "n_recycled": torch.zeros((NA, 2), dtype=torch.int32, device=dev),
+                "learn_step": torch.zeros((), dtype=torch.int64, device=dev)}
+            self.redo_total = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def redo(self, idx=None):
+        """Recycle dead units (ReDo, include/dmdqn.h dmdqn_redo) on the current
+        stream: probe_health(idx), then every hidden unit whose bit of the
+        probe's dead_mask was set on redo_patience calls in a row gets fresh
+        incoming weights, zero outgoing weights and zero Adam moments, in place
+        in params / adam_m / adam_v; the target net, the rings and the random
+        streams are not touched.  The fresh weights are keyed by cfg.seed, the
+        learn step counter and the agent's global index (env_offset + e) * A +
+        j.  Updates redo_streak uint8 [NA, 2, 128], redo_last (the fired units
+        of this call as "recycled" int32 [NA, 2, 4] bits, their counts
+        "n_recycled" int32 [NA, 2], "learn_step"), redo_total int64 [2] and
+        redo_rounds; no host synchronisation.  The caller orders it against
+        other streams' use of the nets (Trainer: quiesce / join_streams).
+        Returns redo_last."""
+        h = self.probe_health(idx)
+        self._redo_alloc()
+        last = self.redo_last
+        K.redo(h["dead_mask"], self.redo_streak, self.params, self.adam_m, self.adam_v, self.H,
+               self.env_offset * self.A, self.cfg.seed, self.learn_step_counter,
+               self.redo_patience, last["recycled"], last["n_recycled"])
+        self.redo_total += last["n_recycled"].sum(0)
+        last["learn_step"].fill_(self.learn_step_counter)
+        self.redo_rounds += 1
+        return last
+
+    def redo_metrics(self, sel=slice(None)):
+        """The "redo" block of learn_metrics(): rounds (calls of redo() so
+        far), learn_step of the last one, recycled [n1, n2] (the units it
+        rewrote per hidden layer, summed over the agents `sel`),
+        agents_touched (how many of them had one) and recycled_total (the
+        run's totals over all agents).  Syncs."""
+        n = self.redo_last["n_recycled"][sel].cpu()
+        return {"rounds": int(self.redo_rounds),
+                "learn_step": int(self.redo_last["learn_step"]),
+                "recycled": [int(x) for x in n.sum(0)],
+                "recycled_total": [int(x) for x in self.redo_total.cpu()],
+                "agents_touched": int((n.sum(1) > 0).sum())}
 
     # -------------------------------------------------------------- act
     def current_epsilon(self):
@@ -1251,6 +1341,7 @@ class BatchedDQN:
         clipping) and "clipped_frac" (the share of agents with norm > clip);
         without it the record has no such keys.  With health_every on and after a
         probe (probe_health) also "health", the block of health_metrics().
+        With redo_every on also "redo", the block of redo_metrics().
         by_variant: a list with one such record
         per sweep variant, reduced over the agents of the variant's replicas,
         plus "variant" (its index), its learning_rate / gamma / tau and "envs"
@@ -1279,6 +1370,8 @@ class BatchedDQN:
                            clipped_frac=float((gn[sel] > clip).double().mean()))
             if self.health_every > 0 and self.health is not None:
                 rec["health"] = self.health_metrics(sel)
+            if self.redo_every > 0:
+                rec["redo"] = self.redo_metrics(sel)
             return rec
         if not by_variant:
             return record(slice(None))
@@ -1296,6 +1389,8 @@ class BatchedDQN:
                     rec.update(grad_norm_mean=None, grad_norm_max=None, clipped_frac=None)
                 if self.health_every > 0 and self.health is not None:
                     rec["health"] = None
+                if self.redo_every > 0:
+                    rec["redo"] = None
             out.append(rec)
         return out
 
@@ -1411,12 +1506,17 @@ class BatchedDQN:
         overwritten, as bits, with those of replica src[e]'s (dmdqn_pbt_exchange,
         in place, on the current stream).  src: host [E]; every source must be
         a fixed point.  Replay rings, staging rings, RNG streams and the env
-        stay each replica's own."""
+        stay each replica's own; the streaks of dead-unit recycling
+        (redo_streak), which describe the nets, move with them."""
         self._pbt_on()
         src = self._pbt_src_checked(src)
         self._pbt_src.copy_(torch.as_tensor(src.astype(np.int32)))
         self._ops.pbt_exchange(self._pbt_src, self.A, self.params, self.target, self.adam_m,
                                self.adam_v, self.target_h)
+        if self.redo_streak is not None:
+            # the streaks of dead probes belong to the nets, not to the replica
+            rows = self.redo_streak.view(self.E, -1)
+            rows.copy_(rows[self._pbt_src.long()])
 
     def pbt_explore(self, src):
         """Explore, round self.pbt_round: every copied replica (src[e] != e)

@@ -82,6 +82,8 @@ KERNEL_SOURCES = {
     "pbt": ["pbt.hip", "common.hpp"],
     # the network health probe (forward reduced to counts; layer sums): off the step's path
     "health": ["health.hip", "learn_img.hpp", "qnet_layout.hpp", "common.hpp"],
+    # dead-unit recycling on the probe's dead mask (ReDo): off the step's path
+    "redo": ["redo.hip", "qnet_layout.hpp", "common.hpp"],
 }
 
 

@@ -18,6 +18,8 @@ needs, so that load + K steps reproduces an uninterrupted run bit-exactly
   trainer   episode / step counters and the current observation
   pbt       population-based training: every replica's hyperparameter values,
             the window's fitness, the round index and the rounds' log
+  redo      dead-unit recycling: every unit's streak of dead probes, the
+            running totals and the number of rounds
 
 Everything is a tensor or a plain int / float / str, so the file loads with
 torch.load(weights_only=True).  Demand tables are NOT stored: they are rebuilt
@@ -45,7 +47,8 @@ _AGENT_TENSORS = ["params", "target", "adam_m", "adam_v", "np_state", "py_state"
 # derived state stale), so load() refuses it.
 _AGENT_FIXED = ["precision", "shared_params", "nn_layers", "replay_buffer_size", "batch_size",
                 "seed", "loss", "target_update_frequency", "count_env_steps", "replay_rows",
-                "ring_spare", "tau", "sweep", "n_step", "pbt", "global_clipnorm"]
+                "ring_spare", "tau", "sweep", "n_step", "pbt", "global_clipnorm", "redo_every",
+                "redo_patience"]
 _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features", "cap_lane",
               "end_ms", "period_ms", "step_duration", "max_sim_time", "action_stride", "scenario",
               "actuated"]
@@ -62,10 +65,13 @@ _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features
 # slots of another value were built from other gradients.  health_every: a
 # checkpoint saved before the health probe existed ran without it; the probe
 # only reads and its outputs are not state, so the key is stored with the rest
-# of the config but a resume may set another value -- it is not in _AGENT_FIXED)
+# of the config but a resume may set another value -- it is not in _AGENT_FIXED.
+# redo_every, redo_patience: a checkpoint saved before dead-unit recycling
+# existed ran without it; the schedule and the patience decide which units are
+# rewritten and when, so both are fixed)
 _DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2,
              "tau": 0.0, "sweep": None, "n_step": 1, "pbt": None, "global_clipnorm": 0.0,
-             "health_every": 0}
+             "health_every": 0, "redo_every": 0, "redo_patience": 1}
 _RING_TENSORS = ["s", "n", "a", "r", "d"]
 
 
@@ -141,6 +147,11 @@ def trainer_state(tr, include_replay=True):
         st["pbt"] = {"values": {k: torch.from_numpy(v.copy()) for k, v in ag.pbt_values.items()},
                      "fitness": ag.fitness.cpu(), "round": int(ag.pbt_round),
                      "log": list(tr.pbt_log)}
+    if ag.redo_every > 0:
+        # dead-unit recycling: every unit's streak of dead probes, the running
+        # totals and the number of rounds; no key without redo
+        st["redo"] = {"streak": ag.redo_streak.cpu(), "total": ag.redo_total.cpu(),
+                      "rounds": int(ag.redo_rounds)}
     return st
 
 
@@ -219,6 +230,13 @@ def load(path, tr):
             if tuple(v.shape) != ag.pbt_values[k].shape or v.dtype != torch.float64:
                 raise ValueError(f"checkpoint pbt.values.{k} {v.dtype}{tuple(v.shape)} != "
                                  f"float64{ag.pbt_values[k].shape}")
+    # (redo_every itself was compared above, so "redo" is present exactly when
+    # this Trainer recycles dead units)
+    if (ag.redo_every > 0) != ("redo" in st):
+        raise ValueError("checkpoint and Trainer disagree on dead-unit recycling")
+    if ag.redo_every > 0:
+        plan("redo", ag.redo_streak, st["redo"]["streak"], "streak")
+        plan("redo", ag.redo_total, st["redo"]["total"], "total")
     # the restore writes on the caller's stream: order it after everything the
     # trainer queued on its side stream (the "env" schedule's side learn may
     # still be updating its agents' weights and Adam slots -- ADVICE r5)
@@ -242,6 +260,8 @@ def load(path, tr):
         ag._pbt_upload()
         ag.pbt_round = int(st["pbt"]["round"])
         tr.pbt_log = [dict(r) for r in st["pbt"]["log"]]
+    if ag.redo_every > 0:
+        ag.redo_rounds = int(st["redo"]["rounds"])
     ag._refresh_params_h()  # the 16-bit copies are derived from the f32 nets
     ag._refresh_target_h()
     tr.obs = st["obs"].to(env.device)

@@ -45,6 +45,47 @@ __host__ __device__ constexpr int qn_w1(int out, int in) {
                       : QN_DT * H + out;
 }
 
+// The inverses (k_redo classifies a float4 chunk of the layout by the neuron
+// and the fan-in values it holds).  An offset that is a multiple of 4 starts 4
+// consecutive fan-in values of one neuron in both tiled blocks.
+struct QnOutIn {
+    int out, in;
+};
+
+// (out, in) of offset `off` in a tiled [N][K] block: the inverse of qn_wt.
+__host__ __device__ constexpr QnOutIn qn_wt_inv(int off, int K) {
+    return QnOutIn{(((off >> 8) / (K >> 4)) << 4) + ((off >> 3) & 15),
+                   (((off >> 8) % (K >> 4)) << 4) + (((off >> 7) & 1) << 3) + (off & 7)};
+}
+
+// (out, in) of offset `off` in the W1 block of an H-neuron layer: the inverse of
+// qn_w1 (off < QN_D * H; the feature-88 column is the block's last H floats).
+template <int H>
+__host__ __device__ constexpr QnOutIn qn_w1_inv(int off) {
+    return off < QN_DT * H
+               ? QnOutIn{((off / (QN_DT * 16)) << 4) + ((off >> 3) & 15),
+                         (((off % (QN_DT * 16)) >> 7) << 3) + (off & 7)}
+               : QnOutIn{off - QN_DT * H, QN_DT};
+}
+
+constexpr bool qn_wt_round_trip(int out, int in, int K) {
+    return qn_wt_inv(qn_wt(out, in, K), K).out == out && qn_wt_inv(qn_wt(out, in, K), K).in == in;
+}
+template <int H>
+constexpr bool qn_w1_round_trip(int out, int in) {
+    return qn_w1_inv<H>(qn_w1<H>(out, in)).out == out && qn_w1_inv<H>(qn_w1<H>(out, in)).in == in;
+}
+static_assert(qn_wt_round_trip(0, 0, 128) && qn_wt_round_trip(127, 127, 128) &&
+                  qn_wt_round_trip(17, 40, 128) && qn_wt_round_trip(96, 9, 128) &&
+                  qn_wt_round_trip(63, 63, 64) && qn_wt_round_trip(31, 8, 64),
+              "qn_wt_inv inverts qn_wt");
+static_assert(qn_w1_round_trip<128>(0, 0) && qn_w1_round_trip<128>(127, 87) &&
+                  qn_w1_round_trip<128>(127, 88) && qn_w1_round_trip<128>(0, 88) &&
+                  qn_w1_round_trip<128>(17, 80) && qn_w1_round_trip<128>(64, 15) &&
+                  qn_w1_round_trip<128>(5, 40) && qn_w1_round_trip<64>(63, 87) &&
+                  qn_w1_round_trip<64>(33, 88),
+              "qn_w1_inv inverts qn_w1");
+
 template <int H>
 struct QL {
     static constexpr int oW1T = 0;

@@ -310,3 +310,31 @@ def layer_norms(x, hidden, y=None, eps=0.0, out=None):
         out = torch.empty((x.shape[0], NORM_VARS), dtype=torch.float64, device=x.device)
     _ops().layer_norms(x, y, float(eps), 0 if y is None else 1, int(hidden), out)
     return out
+
+
+# ------------------------------------------------------------------ dead-unit recycling (ReDo)
+# HeUniform limits sqrt(6 / fan_in) of the fresh weights, as the float32 the
+# kernel multiplies with (include/dmdqn.h dmdqn_redo)
+REDO_LIM1 = float(np.float32(np.sqrt(6.0 / 89.0)))    # bits 1048899646
+REDO_LIM2 = float(np.float32(np.sqrt(6.0 / 128.0)))   # bits 1046328279
+
+
+def redo(dead_mask, streak, params, adam_m, adam_v, hidden, agent0, seed, rnd, patience,
+         recycled=None, n_recycled=None, lim1=REDO_LIM1, lim2=REDO_LIM2):
+    """Recycle the hidden units that were dead on `patience` probes in a row
+    (dmdqn_redo, current stream): dead_mask int32 [NA, 2, 4] (a probe's),
+    streak uint8 [NA, 2, 128] in / out; writes params, adam_m, adam_v in place
+    and recycled int32 [NA, 2, 4] (the fired units as bits), n_recycled int32
+    [NA, 2].  agent0: the global index of agent 0; seed (u64) and rnd (u32, the
+    learn step counter) key the fresh weights.  Allocates the outputs that are
+    not given; returns (recycled, n_recycled)."""
+    NA, dev = params.shape[0], params.device
+    if recycled is None:
+        recycled = torch.empty((NA, 2, 4), dtype=torch.int32, device=dev)
+    if n_recycled is None:
+        n_recycled = torch.empty((NA, 2), dtype=torch.int32, device=dev)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    _ops().redo(dead_mask, streak, params, adam_m, adam_v, int(hidden), int(agent0),
+                seed - (1 << 64) if seed >= 1 << 63 else seed, int(rnd) & 0xFFFFFFFF,
+                int(patience), float(lim1), float(lim2), recycled, n_recycled)
+    return recycled, n_recycled

@@ -790,12 +790,45 @@ void layer_norms(const Tensor &x, const OptT &y, double eps, int64_t mode, int64
           "dmdqn_layer_norms");
 }
 
+// ---------------------------------------------------------------- dead-unit recycling
+// ReDo on the probe's dead mask (include/dmdqn.h dmdqn_redo): streak uint8
+// [NA, 2, 128], recycled int32 [NA, 2, 4] (the uint32 words as bits), n_recycled
+// int32 [NA, 2].  Writes streak, params, adam_m, adam_v and the two outputs.
+void redo(const Tensor &dead_mask, Tensor &streak, Tensor &params, Tensor &adam_m, Tensor &adam_v,
+          int64_t hidden, int64_t agent0, int64_t seed, int64_t round, int64_t patience,
+          double lim1, double lim2, Tensor &recycled, Tensor &n_recycled) {
+    TORCH_CHECK(params.dim() == 2, "params must be [NA, P]");
+    const int64_t NA = params.size(0), P = params.size(1);
+    TORCH_CHECK(NA > 0, "params must be [NA, P] with NA > 0");
+    TORCH_CHECK(round >= 0 && round <= (int64_t)UINT32_MAX, "round out of uint32 range");
+    dmdqn_redo_args a{};
+    a.NA = int32_of(NA, "NA"); a.P = int32_of(P, "P"); a.hidden = int32_of(hidden, "hidden");
+    a.agent0 = int32_of(agent0, "agent0"); a.patience = int32_of(patience, "patience");
+    a.round = (uint32_t)round; a.seed = (uint64_t)seed;
+    a.lim1 = (float)lim1; a.lim2 = (float)lim2;
+    a.dead_mask = dptr<const uint32_t>(dead_mask, at::kInt, "dead_mask", NA * 2 * 4);
+    a.streak = dptr<uint8_t>(streak, at::kByte, "streak", NA * 2 * hidden);
+    a.params = dptr<float>(params, at::kFloat, "params");
+    a.adam_m = dptr<float>(adam_m, at::kFloat, "adam_m", NA * P);
+    a.adam_v = dptr<float>(adam_v, at::kFloat, "adam_v", NA * P);
+    a.recycled = dptr<uint32_t>(recycled, at::kInt, "recycled", NA * 2 * 4);
+    a.n_recycled = dptr<int32_t>(n_recycled, at::kInt, "n_recycled", NA * 2);
+    TORCH_CHECK(dead_mask.device() == params.device() && streak.device() == params.device() &&
+                    adam_m.device() == params.device() && adam_v.device() == params.device() &&
+                    recycled.device() == params.device() && n_recycled.device() == params.device(),
+                "every tensor must be on the device of params");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    check(dmdqn_redo(&a, stream_of(params)), "dmdqn_redo");
+}
+
 // Meta kernels: the ops only mutate their (a!) arguments, so tracing needs no
 // shape function beyond "nothing is returned".
 void pbt_score_meta(const Tensor &, Tensor &) {}
 void net_probe_meta(const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, int64_t,
                     Tensor &, Tensor &, const OptT &) {}
 void layer_norms_meta(const Tensor &, const OptT &, double, int64_t, int64_t, Tensor &) {}
+void redo_meta(const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, int64_t, int64_t, int64_t,
+               int64_t, int64_t, double, double, Tensor &, Tensor &) {}
 void pbt_select_meta(const Tensor &, int64_t, Tensor &, Tensor &) {}
 void pbt_exchange_meta(const Tensor &, int64_t, Tensor &, Tensor &, Tensor &, Tensor &,
                        const OptT &) {}
@@ -988,6 +1021,11 @@ TORCH_LIBRARY(dmdqn, m) {
           "int precision, Tensor(a!) counts, Tensor(b!) stats, Tensor(c!)? dead_mask=None) -> ()");
     m.def("layer_norms(Tensor x, Tensor? y, float eps, int mode, int hidden, "
           "Tensor(a!) out) -> ()");
+    // dead-unit recycling on the probe's dead mask (ReDo; docs/improvements.md item 3,
+    // "improve weight inits"; nothing in the reference's code does it)
+    m.def("redo(Tensor dead_mask, Tensor(a!) streak, Tensor(b!) params, Tensor(c!) adam_m, "
+          "Tensor(d!) adam_v, int hidden, int agent0, int seed, int round, int patience, "
+          "float lim1, float lim2, Tensor(e!) recycled, Tensor(f!) n_recycled) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
@@ -1019,6 +1057,7 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("pbt_exchange", &pbt_exchange);
     m.impl("net_probe", &net_probe);
     m.impl("layer_norms", &layer_norms);
+    m.impl("redo", &redo);
 }
 
 TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
@@ -1050,4 +1089,5 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("pbt_exchange", &pbt_exchange_meta);
     m.impl("net_probe", &net_probe_meta);
     m.impl("layer_norms", &layer_norms_meta);
+    m.impl("redo", &redo_meta);
 }

@@ -271,8 +271,10 @@ class Trainer:
         # behind: sync_outputs() orders a read under another stream after it
         self._step_stream = torch.cuda.current_stream(self.env.device)
         st = self._step(collect_stats)
-        n = self.agent.health_every
-        if n > 0 and st.loss_launched and self.agent.learn_step_counter % n == 0:
+        n, r = self.agent.health_every, self.agent.redo_every
+        if r > 0 and st.loss_launched and self.agent.learn_step_counter % r == 0:
+            self._redo()  # (its probe is also health_every's, if that falls on this learn)
+        elif n > 0 and st.loss_launched and self.agent.learn_step_counter % n == 0:
             self._probe_health()
         if self.agent.pbt is not None:
             self._pbt_after_step()
@@ -304,6 +306,19 @@ class Trainer:
             # the next side learn writes its agents' nets on the side stream,
             # which nothing else orders behind this stream's reads of them
             self.side.wait_stream(torch.cuda.current_stream(self.env.device))
+
+    def _redo(self):
+        """Dead-unit recycling (AgentConfig.redo_every) behind the learn this
+        step began, on the caller's stream: the probe, then the in-place
+        rewrite of the fired units' weights and Adam moments (agent.redo).  It
+        writes the nets, so it runs in _pbt_round's bracket: quiesce() (a
+        held-back paired learn is launched; the side stream's env step, draws
+        and side learn are done with the nets, the rings and the index
+        buffers) before it and join_streams() (the side stream's next work
+        waits for it) after it."""
+        self.quiesce()
+        self.agent.redo()
+        self.join_streams()
 
     def _pbt_after_step(self):
         """Population-based training, on the caller's stream: the step's reward

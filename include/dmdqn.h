@@ -820,6 +820,71 @@ int dmdqn_net_probe(const dmdqn_probe_args *args, void *stream);
 int dmdqn_layer_norms(const float *x, const float *y, float eps, int mode, int NW, int P,
                       int hidden, double *out, void *stream);
 
+/* ------------------------------------------------------------------ dead-unit recycling (ReDo)
+ * Not in the reference's code; its to-do list has "improve weight inits"
+ * (docs/improvements.md item 3).  The rule is ReDo with tau = 0 (Sokar et al.
+ * 2023, "The Dormant Neuron Phenomenon in Deep RL") on the probe's dead_mask: a
+ * hidden unit that was dead on `patience` probes in a row gets fresh incoming
+ * weights, zero outgoing weights and zero Adam moments.
+ *
+ * When a unit fires.  streak uint8 [NA][2][128], one byte per agent, hidden
+ * layer l and unit u.  With d = bit u of dead_mask[agent][l]:
+ *     s = d ? min(s + 1, 255) : 0;   fire = s >= patience;   if (fire) s = 0.
+ * R1 / R2 = the fired units of layer 1 / 2 of the agent.  recycled uint32
+ * [NA][2][4] receives them as bits (dead_mask's format), n_recycled int32
+ * [NA][2] their counts.
+ *
+ * What changes, in Keras terms W[in][out] (only params, adam_m, adam_v; the
+ * target net, b3, rings and random streams are not touched):
+ *     W1[:, u] fresh (all 89), b1[u] = 0                        for u in R1;
+ *     W2[i, o] = 0 when i in R1, else fresh when o in R2        (zero wins on
+ *         the overlap: the forward on the probed batch keeps its value
+ *         whatever the fresh values are);
+ *     b2[o] = 0, W3[o, :] = 0                                   for o in R2;
+ *     adam_m = adam_v = +0.0 wherever the parameter was written above.
+ * Every other position of the three arrays keeps its bits.
+ *
+ * Fresh values are HeUniform with the variance 2 / fan_in of the HeNormal that
+ * new nets start from (uniform so that both sides are exact without a device
+ * logf / cosf), drawn from a stateless counter hash (u64, wrapping):
+ *     mix64(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *               x *= 0x94D049BB133111EB; x ^= x >> 31
+ *     G = 0x9E3779B97F4A7C15
+ *     k = mix64(seed + G * (round + 1))
+ *     c = (((agent0 + agent) * 2 + layer) * 128 + unit) * 128 + in
+ *     z = mix64(k + G * (c + 1));   u24 = z >> 40
+ *     t = float((int)(2 * u24 + 1 - 2^24)) * 2^-24    (exact: odd, |.| < 2^24)
+ *     w = fl32(lim * t)                                (one f32 multiply, no fma)
+ * layer 0: unit u of R1, in 0..88, lim = lim1 = float32(sqrt(6 / 89));
+ * layer 1: unit o of R2, in 0..127, lim = lim2 = float32(sqrt(6 / 128)).
+ * t lies in (-1, 1), is never 0 and is symmetric.  agent0 is the global index
+ * of agent 0 ((env_offset) * A of a sharded run), so a rank draws what one
+ * process gives those replicas.
+ *
+ * One 256-thread workgroup per agent; one whose agent fired nothing exits after
+ * the streak update (32 + 256 B read, 256 + 40 B written).  Otherwise it walks
+ * the agent's P / 4 float4 chunks, decides each from the fired masks alone,
+ * skips the untouched, stores the wholly changed without a load and
+ * read-modify-writes the mixed ones; 16-B accesses, no atomics.  Refused on the
+ * host (DMDQN_EINVAL, before any launch): null pointers, NA <= 0, hidden !=
+ * 128, P != 28,548, patience outside 1..255, agent0 < 0, an array that is not
+ * 16-B aligned (n_recycled: 8-B). */
+typedef struct dmdqn_redo_args {
+    int32_t NA, P, hidden;
+    int32_t agent0;            /* global index of agent 0 */
+    int32_t patience;          /* 1..255 */
+    uint32_t round;            /* the learn step counter at the probe */
+    uint64_t seed;
+    float lim1, lim2;
+    const uint32_t *dead_mask; /* [NA][2][4] */
+    uint8_t *streak;           /* [NA][2][128] in/out */
+    float *params;             /* [NA][P] online nets, device layout; in/out */
+    float *adam_m, *adam_v;    /* [NA][P] in/out */
+    uint32_t *recycled;        /* [NA][2][4] out */
+    int32_t *n_recycled;       /* [NA][2] out */
+} dmdqn_redo_args;
+int dmdqn_redo(const dmdqn_redo_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,7 +100,7 @@ def create_agents(tl_junctions, config=AGENT_CONFIG):
 
 
 def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG, n_step=1,
-                  global_clipnorm=0.0, health_every=0):
+                  global_clipnorm=0.0, health_every=0, redo_every=0, redo_patience=1):
     """AGENT_CONFIG with the target-network rule of --tau /
     --target_update_frequency: soft updates (dqn_agent.py:372-373, 389-399) of
     rate tau after every learn, hard syncs every target_update_frequency learns
@@ -109,8 +109,12 @@ def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG, n_
     and --global_clipnorm: gradient clipping by global norm
     (AgentConfig.global_clipnorm; 0 = off, the reference's optimizer); and
     --health_every: the network health probe after every N-th learn
-    (AgentConfig.health_every; 0 = off)."""
+    (AgentConfig.health_every; 0 = off); and --redo_every / --redo_patience:
+    dead-unit recycling after every N-th learn (AgentConfig.redo_every; 0 =
+    off)."""
     config = dict(config)
+    if redo_every:
+        config["redo_every"], config["redo_patience"] = int(redo_every), int(redo_patience)
     if health_every:
         config["health_every"] = int(health_every)
     if n_step != 1:
@@ -218,7 +222,7 @@ def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenar
 def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, scenario=None,
                   shared=False, save_dir=None, resume=None, log_every=20, loss="mse",
                   actuated=False, tau=0.0, target_update_frequency=None, sweep=None, n_step=1,
-                  pbt=None, global_clipnorm=0.0, health_every=0):
+                  pbt=None, global_clipnorm=0.0, health_every=0, redo_every=0, redo_patience=1):
     """E env replicas of the loop on the GPU.  The optional JSONL carries the
     reference's learn scalars (dqn_agent.py:361-370: loss, epsilon,
     q_values_mean / _std, action_distribution) and its per-step rewards with
@@ -233,7 +237,9 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     then carry grad_norm_mean / grad_norm_max / clipped_frac too.  health_every
     (AgentConfig.health_every): once a probe has run, each record's learn
     scalars (per variant too) carry the "health" block of the last probe, and
-    the final line's variants their dead_frac and update_ratio.  pbt
+    the final line's variants their dead_frac and update_ratio.  redo_every /
+    redo_patience (AgentConfig.redo_every): each record's learn scalars carry
+    the "redo" block (rounds, the units recycled last round and in total).  pbt
     (AgentConfig.pbt, parse_pbt): population-based training; the variants then
     dissolve, so a record written at a round carries that round's pbt_log
     entry, the final line a "pbt" block (rounds, copies, the best replica of
@@ -244,7 +250,9 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     from dmdqn_amd.trainer import Trainer
     cfg = AgentConfig.from_dict(target_config(tau, target_update_frequency, n_step=n_step,
                                               global_clipnorm=global_clipnorm,
-                                              health_every=health_every))
+                                              health_every=health_every,
+                                              redo_every=redo_every,
+                                              redo_patience=redo_patience))
     cfg.precision, cfg.seed, cfg.shared_params, cfg.loss = precision, seed, shared, loss
     cfg.sweep, cfg.pbt = sweep, pbt
     tr = Trainer(EnvConfig(rows=rows, cols=cols, num_envs=envs, seed=seed, scenario=scenario,
@@ -423,12 +431,22 @@ def main():
                          "and active ReLU units, non-finite activations, weight norms, "
                          "update-to-weight ratios); the metrics gain a \"health\" block.  0 = "
                          "off.  fp16 / bf16 independent nets")
+    ap.add_argument("--redo_every", type=int, default=0, metavar="N",
+                    help="batched only: after each N-th learn probe every agent's network and "
+                         "recycle its dead ReLU units (ReDo: fresh incoming weights, zero "
+                         "outgoing weights, zero Adam moments); the metrics gain a \"redo\" "
+                         "block.  0 = off.  fp16 / bf16 independent nets")
+    ap.add_argument("--redo_patience", type=int, default=1, metavar="K",
+                    help="with --redo_every: a unit is recycled once it was dead on K probes in "
+                         "a row (1..255)")
     args = ap.parse_args()
     try:
         sweep = parse_sweep(args.sweep)
         pbt = parse_pbt(args.pbt, args.pbt_perturb)
-        from dmdqn_amd.agent import check_clipnorm, check_health_every, check_n_step
+        from dmdqn_amd.agent import (check_clipnorm, check_health_every, check_n_step,
+                                     check_redo)
         check_health_every(args.health_every)
+        check_redo(args.redo_every, args.redo_patience)
         check_n_step(args.n_step, AGENT_CONFIG["replay_buffer_size"])
         check_clipnorm(args.global_clipnorm)
     except ValueError as e:
@@ -445,6 +463,10 @@ def main():
         ap.error("--health_every needs --batched")
     if args.health_every and (args.shared or args.precision == "fp32"):
         ap.error("--health_every runs with --precision fp16 / bf16, not with --shared")
+    if args.redo_every and not args.batched:
+        ap.error("--redo_every needs --batched")
+    if args.redo_every and (args.shared or args.precision == "fp32"):
+        ap.error("--redo_every runs with --precision fp16 / bf16, not with --shared")
     logging.basicConfig(level=logging.INFO)
     rows, cols = (int(x) for x in args.grid.split("x"))
     scenario = args.scenario
@@ -456,7 +478,8 @@ def main():
         train_batched(args.episodes, rows, cols, args.envs, args.precision, args.seed, args.metrics,
                       scenario, args.shared, args.save_dir, args.resume, args.log_every, args.loss,
                       args.actuated, args.tau, args.target_update_frequency, sweep, args.n_step,
-                      pbt, args.global_clipnorm, args.health_every)
+                      pbt, args.global_clipnorm, args.health_every, args.redo_every,
+                      args.redo_patience)
     else:
         train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir,
                      args.tau, args.target_update_frequency, args.n_step)
