@@ -300,6 +300,27 @@ def check_redo(every, patience):
     return int(every), int(patience)
 
 
+# rule-based behaviour policies (kernels.RULES, include/dmdqn.h dmdqn_act_rule)
+BEHAVIORS = tuple(K.RULES)
+
+
+def check_behavior(behavior, steps, eps):
+    """(behavior, behavior_steps, behavior_eps) checked, or ValueError:
+    behavior None or one of BEHAVIORS, behavior_steps an integer >= 0 (0 = the
+    whole run), behavior_eps a number in [0, 1]."""
+    if behavior is not None and behavior not in BEHAVIORS:
+        raise ValueError(f"behavior must be None or one of {list(BEHAVIORS)}, got {behavior!r}")
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or int(steps) < 0:
+        raise ValueError(f"behavior_steps must be an integer >= 0, got {steps!r}")
+    try:
+        e = float(eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"behavior_eps must be a number in [0, 1], got {eps!r}") from None
+    if not 0.0 <= e <= 1.0:  # (false for NaN too)
+        raise ValueError(f"behavior_eps must be in [0, 1], got {eps!r}")
+    return behavior, int(steps), e
+
+
 # the Keras variables of one net, in get_weights order (dmdqn_layer_norms' columns)
 VARIABLES = ("W1", "b1", "W2", "b2", "W3", "b3")
 
@@ -610,6 +631,21 @@ class AgentConfig:
     # Not sweep keys.
     redo_every: int = 0
     redo_patience: int = 1
+    # rule-based behaviour policy (include/dmdqn.h dmdqn_act_rule): while it is
+    # active -- for the first behavior_steps env steps, or the whole run with
+    # behavior_steps 0 -- act_inputs() hands the act the rule's actions
+    # ("longest_queue" / "max_pressure", from the current observation) as its
+    # greedy actions and behavior_eps as its epsilon: every agent draws rand()
+    # as ever and takes a uniform action below behavior_eps, the rule's
+    # otherwise.  The replay rings then fill with a controller's transitions
+    # instead of uniformly random ones (A-1: epsilon stays 1.0 on the
+    # reference training path).  Afterwards everything is as without it.
+    # learn_metrics() gains a "behavior" block.  None = off: nothing is
+    # allocated or launched.  Runs with every net configuration (the rule needs
+    # no net); under a Trainer with overlap "none" or "env".  Not sweep keys.
+    behavior: Optional[str] = None
+    behavior_steps: int = 0
+    behavior_eps: float = 0.1
 
     @classmethod
     def from_dict(cls, d):
@@ -707,6 +743,11 @@ class BatchedDQN:
         # mask and counts, the running totals; and the number of calls
         self.redo_streak = self.redo_last = self.redo_total = None
         self.redo_rounds = 0
+        # rule-based behaviour policy: the checked config and the env steps
+        # taken so far (remember() / remembered() count them; checkpointed)
+        self.behavior, self.behavior_steps, self.behavior_eps = check_behavior(
+            cfg.behavior, cfg.behavior_steps, cfg.behavior_eps)
+        self.behavior_step_count = 0
         if int(cfg.target_update_frequency) < 0:
             raise ValueError("target_update_frequency must be >= 0 (0 = never hard-sync)")
         if cfg.shared_params and (cfg.precision != "fp16" or H != 128):
@@ -1059,6 +1100,12 @@ class BatchedDQN:
                 "recycled_total": [int(x) for x in self.redo_total.cpu()],
                 "agents_touched": int((n.sum(1) > 0).sum())}
 
+    def behavior_metrics(self):
+        """The "behavior" block of learn_metrics(): the configured policy, its
+        epsilon and whether the next act still takes it."""
+        return {"policy": self.behavior, "eps": float(self.behavior_eps),
+                "active": bool(self.behavior_active())}
+
     # -------------------------------------------------------------- act
     def current_epsilon(self):
         """dqn_agent.py:258-261 (global_step_count never moves on the reference
@@ -1076,16 +1123,34 @@ class BatchedDQN:
         eps, greedy, out = self.act_inputs(obs, eps)
         return K.act(self.np_state, self.A, eps=eps, n_actions=N_ACTIONS, greedy=greedy, out=out)
 
+    def behavior_active(self):
+        """Whether the next training act takes the behaviour policy's actions
+        (AgentConfig.behavior): fewer than behavior_steps env steps stored so
+        far, or behavior_steps 0."""
+        return self.behavior is not None and (
+            self.behavior_steps == 0 or self.behavior_step_count < self.behavior_steps)
+
     def act_inputs(self, obs, eps=None):
         """What a fused env step (TrafficEnv.step_fused) needs to draw act()'s
         actions itself: (eps, greedy or None, the actions buffer to fill).
-        The greedy forward (eps < 1) is launched here, as act() does."""
+        The greedy forward (eps < 1) is launched here, as act() does.  While a
+        behaviour policy is active (AgentConfig.behavior; training acts only,
+        eps None) the epsilon is behavior_eps and the greedy actions are the
+        rule's, from the observation alone (the grid enters only as its A
+        junctions): one act_rule launch in place of the forward."""
+        rule = eps is None and self.behavior_active()
         eps = self.current_epsilon() if eps is None else float(eps)
+        if rule:  # (the nets' schedule above moved as without the policy)
+            eps = self.behavior_eps
         greedy = None
         if eps < 1.0:
-            self._ops.q_argmax(self.params, self.H, PRECISIONS[self.cfg.precision],
-                               obs.reshape(self.NA, D_IN).contiguous(), self.greedy, None,
-                               self.shared)
+            if rule:
+                K.act_rule(obs.reshape(self.E, self.A, D_IN).contiguous(), 1, self.A,
+                           self.behavior, out=self.greedy)
+            else:
+                self._ops.q_argmax(self.params, self.H, PRECISIONS[self.cfg.precision],
+                                   obs.reshape(self.NA, D_IN).contiguous(), self.greedy, None,
+                                   self.shared)
             greedy = self.greedy
         self._act_i = (self._act_i + 1) % self.OUT_BUFS
         self.actions = self._act_bufs[self._act_i]
@@ -1098,6 +1163,7 @@ class BatchedDQN:
         self.store_ring.advance()
         self.commit_nstep()
         self.ring.poll()
+        self.behavior_step_count += 1
         if self.cfg.count_env_steps:
             self.global_step_count += 1
 
@@ -1125,6 +1191,7 @@ class BatchedDQN:
                               actions.reshape(NA), rewards.reshape(NA), d)
         self.commit_nstep()
         self.ring.poll()  # raises (one store late, no stall) on a non-int8 observation
+        self.behavior_step_count += 1
         if self.cfg.count_env_steps:
             self.global_step_count += 1
 
@@ -1342,6 +1409,8 @@ class BatchedDQN:
         without it the record has no such keys.  With health_every on and after a
         probe (probe_health) also "health", the block of health_metrics().
         With redo_every on also "redo", the block of redo_metrics().
+        With a behaviour policy configured also "behavior", the block of
+        behavior_metrics().
         by_variant: a list with one such record
         per sweep variant, reduced over the agents of the variant's replicas,
         plus "variant" (its index), its learning_rate / gamma / tau and "envs"
@@ -1372,6 +1441,8 @@ class BatchedDQN:
                 rec["health"] = self.health_metrics(sel)
             if self.redo_every > 0:
                 rec["redo"] = self.redo_metrics(sel)
+            if self.behavior is not None:
+                rec["behavior"] = self.behavior_metrics()
             return rec
         if not by_variant:
             return record(slice(None))
@@ -1391,6 +1462,8 @@ class BatchedDQN:
                     rec["health"] = None
                 if self.redo_every > 0:
                     rec["redo"] = None
+                if self.behavior is not None:
+                    rec["behavior"] = self.behavior_metrics()
             out.append(rec)
         return out
 

@@ -84,6 +84,9 @@ KERNEL_SOURCES = {
     "health": ["health.hip", "learn_img.hpp", "qnet_layout.hpp", "common.hpp"],
     # dead-unit recycling on the probe's dead mask (ReDo): off the step's path
     "redo": ["redo.hip", "qnet_layout.hpp", "common.hpp"],
+    # the rule-based controllers (longest queue, max pressure): one small launch in place of
+    # the greedy forward; sim.hpp for the signal program its lane groups are derived from
+    "rule": ["rule.hip", "sim.hpp", "common.hpp"],
 }
 
 

@@ -20,6 +20,8 @@ needs, so that load + K steps reproduces an uninterrupted run bit-exactly
             the window's fitness, the round index and the rounds' log
   redo      dead-unit recycling: every unit's streak of dead probes, the
             running totals and the number of rounds
+  behavior  the rule-based behaviour policy: the env steps taken so far (what
+            decides when the policy hands over)
 
 Everything is a tensor or a plain int / float / str, so the file loads with
 torch.load(weights_only=True).  Demand tables are NOT stored: they are rebuilt
@@ -48,7 +50,7 @@ _AGENT_TENSORS = ["params", "target", "adam_m", "adam_v", "np_state", "py_state"
 _AGENT_FIXED = ["precision", "shared_params", "nn_layers", "replay_buffer_size", "batch_size",
                 "seed", "loss", "target_update_frequency", "count_env_steps", "replay_rows",
                 "ring_spare", "tau", "sweep", "n_step", "pbt", "global_clipnorm", "redo_every",
-                "redo_patience"]
+                "redo_patience", "behavior", "behavior_steps", "behavior_eps"]
 _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features", "cap_lane",
               "end_ms", "period_ms", "step_duration", "max_sim_time", "action_stride", "scenario",
               "actuated"]
@@ -68,10 +70,14 @@ _ENV_FIXED = ["rows", "cols", "num_envs", "env_offset", "seed", "signal_features
 # of the config but a resume may set another value -- it is not in _AGENT_FIXED.
 # redo_every, redo_patience: a checkpoint saved before dead-unit recycling
 # existed ran without it; the schedule and the patience decide which units are
-# rewritten and when, so both are fixed)
+# rewritten and when, so both are fixed.  behavior, behavior_steps,
+# behavior_eps: a checkpoint saved before the behaviour policy existed ran
+# without it; the three decide the actions of the steps to come, so all are
+# fixed)
 _DEFAULTS = {"loss": "mse", "actuated": False, "replay_rows": "int8", "ring_spare": 2,
              "tau": 0.0, "sweep": None, "n_step": 1, "pbt": None, "global_clipnorm": 0.0,
-             "health_every": 0, "redo_every": 0, "redo_patience": 1}
+             "health_every": 0, "redo_every": 0, "redo_patience": 1, "behavior": None,
+             "behavior_steps": 0, "behavior_eps": 0.1}
 _RING_TENSORS = ["s", "n", "a", "r", "d"]
 
 
@@ -152,6 +158,9 @@ def trainer_state(tr, include_replay=True):
         # totals and the number of rounds; no key without redo
         st["redo"] = {"streak": ag.redo_streak.cpu(), "total": ag.redo_total.cpu(),
                       "rounds": int(ag.redo_rounds)}
+    if ag.behavior is not None:
+        # the behaviour policy's step counter; no key without a policy
+        st["behavior"] = {"steps_taken": int(ag.behavior_step_count)}
     return st
 
 
@@ -237,6 +246,9 @@ def load(path, tr):
     if ag.redo_every > 0:
         plan("redo", ag.redo_streak, st["redo"]["streak"], "streak")
         plan("redo", ag.redo_total, st["redo"]["total"], "total")
+    # (behavior itself was compared above)
+    if (ag.behavior is not None) != ("behavior" in st):
+        raise ValueError("checkpoint and Trainer disagree on the behaviour policy")
     # the restore writes on the caller's stream: order it after everything the
     # trainer queued on its side stream (the "env" schedule's side learn may
     # still be updating its agents' weights and Adam slots -- ADVICE r5)
@@ -262,6 +274,8 @@ def load(path, tr):
         tr.pbt_log = [dict(r) for r in st["pbt"]["log"]]
     if ag.redo_every > 0:
         ag.redo_rounds = int(st["redo"]["rounds"])
+    if ag.behavior is not None:
+        ag.behavior_step_count = int(st["behavior"]["steps_taken"])
     ag._refresh_params_h()  # the 16-bit copies are derived from the f32 nets
     ag._refresh_target_h()
     tr.obs = st["obs"].to(env.device)

@@ -18,8 +18,9 @@ __device__ __forceinline__ int phase_dur(int p) {
 // 3 U-turn.  'G' and 'g' are green, 'y' and 'r' stop.  Derived from the
 // phase strings with the link layout of grid_3x3.net.xml:1375-1461
 // (per approach: r, s, s, -, l, t): phases 0, 3, 6, 9 -> 0x11BB, 0x11DD,
-// 0xBB11, 0xDD11, the rest none.
-__device__ __forceinline__ uint32_t green_mask(int p) {
+// 0xBB11, 0xDD11, the rest none.  (constexpr, like opp / right_of / movement
+// below: rule.hip derives the controllers' lane groups from them at compile time.)
+__host__ __device__ __forceinline__ constexpr uint32_t green_mask(int p) {
     uint32_t g = p == 0 ? 0x11BBu : 0u;
     g = p == 3 ? 0x11DDu : g;
     g = p == 6 ? 0xBB11u : g;
@@ -56,11 +57,11 @@ constexpr int kArrive = -2;
 enum { DIR_N = 0, DIR_S = 1, DIR_E = 2, DIR_W = 3 };
 enum { MV_R = 0, MV_S = 1, MV_L = 2, MV_U = 3 };
 
-__device__ __forceinline__ int opp(int d) { return d ^ 1; }
-__device__ __forceinline__ int right_of(int h) {  // n->e, s->w, e->s, w->n
+__host__ __device__ __forceinline__ constexpr int opp(int d) { return d ^ 1; }
+__host__ __device__ __forceinline__ constexpr int right_of(int h) {  // n->e, s->w, e->s, w->n
     return h == DIR_N ? DIR_E : h == DIR_S ? DIR_W : h == DIR_E ? DIR_S : DIR_N;
 }
-__device__ __forceinline__ int movement(int h, int o) {
+__host__ __device__ __forceinline__ constexpr int movement(int h, int o) {
     if (o == h) return MV_S;
     if (o == opp(h)) return MV_U;
     if (o == right_of(h)) return MV_R;

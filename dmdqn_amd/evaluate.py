@@ -11,6 +11,11 @@ of a single batched TrafficEnv:
     np.random.randint(0, 4) alone per agent (test.py:92-93); 'fixed' -- the
     cycle [(action 0, 30 s), (action 2, 30 s)] advanced by step_duration
     before each choice (test.py:93-107, :214-216);
+    not in the reference: 'longest_queue' and 'max_pressure' -- the rule-based
+    controllers (include/dmdqn.h dmdqn_act_rule), the action a pure function
+    of the observation, no random draw; 'program' -- no setPhase at all
+    (action -1 at every junction and step, dmdqn_sim_step): the junctions run
+    the net's own 12-phase program, actuated under EnvConfig.actuated;
   * per episode: total_reward = sum over steps and agents of the env reward,
     avg_reward_per_agent = total / A, avg_step_queue_sum = mean over agent-steps
     of sum(obs[:12]) of the observation the action was chosen from
@@ -32,6 +37,8 @@ from .agent import AgentConfig, BatchedDQN, n_params_keras
 from .env import EnvConfig, TrafficEnv
 
 FIXED_CYCLE = ((0, 30.0), (2, 30.0))  # test.py:214-216
+RULE_MODES = tuple(K.RULES)  # "longest_queue", "max_pressure"
+MODES = ("dqn", "random", "fixed", "program") + RULE_MODES
 
 
 def fixed_cycle_actions(n_steps, step_duration, cycle=FIXED_CYCLE):
@@ -81,10 +88,13 @@ def run_mode(env_cfg: EnvConfig, mode, episodes=10, eval_seed_start=10000, eval_
                        nn_layers=[H, H])
         agent = BatchedDQN(E, A, acfg, device=dev, init_weights=w,
                            streams=(np_state, K.seed_streams(env.seeds, "py", dev)))
-    elif mode not in ("random", "fixed"):
+    elif mode not in MODES:
         raise ValueError(f"unknown mode {mode!r}")
     n_steps = min(max_steps, cfg.max_sim_time // cfg.step_duration)
     fixed = fixed_cycle_actions(n_steps, cfg.step_duration) if mode == "fixed" else None
+    # 'program': the action the sim reads as "no setPhase for this junction"
+    no_action = (torch.full((E, A), -1, dtype=torch.int32, device=dev) if mode == "program"
+                 else None)
     obs = env.reset()
     total = torch.zeros(E, dtype=torch.float64, device=dev)
     qsum = torch.zeros(E, dtype=torch.float64, device=dev)
@@ -100,6 +110,10 @@ def run_mode(env_cfg: EnvConfig, mode, episodes=10, eval_seed_start=10000, eval_
             actions = agent.act(obs, eps=eval_epsilon)
         elif mode == "random":
             actions = K.act(np_state, A, uniform=True)  # test.py:92-93: randint only
+        elif mode in RULE_MODES:
+            actions = K.act_rule(obs, cfg.rows, cfg.cols, mode)
+        elif mode == "program":
+            actions = no_action
         else:
             actions = torch.full((E, A), fixed[step], dtype=torch.int32, device=dev)
         live = (~ended).to(torch.float64)

@@ -338,3 +338,31 @@ def redo(dead_mask, streak, params, adam_m, adam_v, hidden, agent0, seed, rnd, p
                 seed - (1 << 64) if seed >= 1 << 63 else seed, int(rnd) & 0xFFFFFFFF,
                 int(patience), float(lim1), float(lim2), recycled, n_recycled)
     return recycled, n_recycled
+
+
+# ------------------------------------------------------------------ rule-based controllers
+# include/dmdqn.h DMDQN_RULE_*
+RULES = {"longest_queue": 0, "max_pressure": 1}
+
+
+def rule_id(rule):
+    """A rule's name ("longest_queue" / "max_pressure") or number as the
+    integer dmdqn_act_rule takes; an unknown name raises ValueError (an
+    unknown number is refused by the entry point, with its message)."""
+    if isinstance(rule, str):
+        if rule not in RULES:
+            raise ValueError(f"unknown rule {rule!r}: one of {sorted(RULES)}")
+        return RULES[rule]
+    return int(rule)
+
+
+def act_rule(obs, R, C, rule, out=None, score=None):
+    """The rule-based controller's action for every agent (dmdqn_act_rule,
+    current stream): obs f32 [E, R*C, 89] -> int32 [E, R*C], in act()'s
+    `greedy` format.  rule: "longest_queue" / "max_pressure" or the integer.
+    score: optional int32 [E, R*C, 4] that receives the four scores.
+    Allocates `out` when it is not given and returns it."""
+    if out is None:
+        out = torch.empty(tuple(obs.shape[:2]), dtype=torch.int32, device=obs.device)
+    _ops().act_rule(obs, int(R), int(C), rule_id(rule), out, score)
+    return out

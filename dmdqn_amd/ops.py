@@ -40,6 +40,7 @@ ENTRY_POINTS = {
     "dmdqn_pbt_exchange": "pbt_exchange",
     "dmdqn_net_probe": "net_probe", "dmdqn_layer_norms": "layer_norms",
     "dmdqn_redo": "redo",
+    "dmdqn_act_rule": "act_rule",
 }
 
 TORCH_LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"libdmdqn_torch{_lib._SUFFIX}.so")

@@ -821,6 +821,29 @@ void redo(const Tensor &dead_mask, Tensor &streak, Tensor &params, Tensor &adam_
     check(dmdqn_redo(&a, stream_of(params)), "dmdqn_redo");
 }
 
+// ---------------------------------------------------------------- rule-based controllers
+// Longest-queue / max-pressure actions from the observations (include/dmdqn.h
+// dmdqn_act_rule): obs f32 [E, R*C, 89], actions int32 [E*R*C] (any shape),
+// score int32 [E*R*C, 4] or None.  The grid, E and the rule are refused by the
+// C entry point (its message is raised), before any launch.
+void act_rule(const Tensor &obs, int64_t R, int64_t C, int64_t rule, Tensor &actions,
+              const OptT &score) {
+    TORCH_CHECK(obs.dim() == 3 && obs.size(2) == DMDQN_OBS_DIM, "obs must be [E, R*C, 89]");
+    const int64_t E = obs.size(0), A = obs.size(1);
+    TORCH_CHECK(R < 1 || C < 1 || A == R * C, "obs must be [E, R*C, 89]: ", A, " agents for a ", R,
+                "x", C, " grid");
+    auto o = dptr<const float>(obs, at::kFloat, "obs");
+    auto a = dptr<int32_t>(actions, at::kInt, "actions", E * A);
+    auto sc = optr<int32_t>(score, at::kInt, "score", E * A * 4);
+    TORCH_CHECK(actions.device() == obs.device() &&
+                    (!score.has_value() || score->device() == obs.device()),
+                "every tensor must be on the device of obs");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(obs.device());
+    check(dmdqn_act_rule(int32_of(R, "R"), int32_of(C, "C"), int32_of(E, "E"),
+                         int32_of(rule, "rule"), o, a, sc, stream_of(obs)),
+          "dmdqn_act_rule");
+}
+
 // Meta kernels: the ops only mutate their (a!) arguments, so tracing needs no
 // shape function beyond "nothing is returned".
 void pbt_score_meta(const Tensor &, Tensor &) {}
@@ -829,6 +852,7 @@ void net_probe_meta(const Tensor &, const Tensor &, const Tensor &, int64_t, int
 void layer_norms_meta(const Tensor &, const OptT &, double, int64_t, int64_t, Tensor &) {}
 void redo_meta(const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, int64_t, int64_t, int64_t,
                int64_t, int64_t, double, double, Tensor &, Tensor &) {}
+void act_rule_meta(const Tensor &, int64_t, int64_t, int64_t, Tensor &, const OptT &) {}
 void pbt_select_meta(const Tensor &, int64_t, Tensor &, Tensor &) {}
 void pbt_exchange_meta(const Tensor &, int64_t, Tensor &, Tensor &, Tensor &, Tensor &,
                        const OptT &) {}
@@ -1026,6 +1050,10 @@ TORCH_LIBRARY(dmdqn, m) {
     m.def("redo(Tensor dead_mask, Tensor(a!) streak, Tensor(b!) params, Tensor(c!) adam_m, "
           "Tensor(d!) adam_v, int hidden, int agent0, int seed, int round, int patience, "
           "float lim1, float lim2, Tensor(e!) recycled, Tensor(f!) n_recycled) -> ()");
+    // rule-based controllers in dmdqn_act's greedy format (longest queue, max pressure;
+    // nothing in the reference's code has them)
+    m.def("act_rule(Tensor obs, int R, int C, int rule, Tensor(a!) actions, "
+          "Tensor(b!)? score) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
@@ -1058,6 +1086,7 @@ TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
     m.impl("net_probe", &net_probe);
     m.impl("layer_norms", &layer_norms);
     m.impl("redo", &redo);
+    m.impl("act_rule", &act_rule);
 }
 
 TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
@@ -1090,4 +1119,5 @@ TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
     m.impl("net_probe", &net_probe_meta);
     m.impl("layer_norms", &layer_norms_meta);
     m.impl("redo", &redo_meta);
+    m.impl("act_rule", &act_rule_meta);
 }

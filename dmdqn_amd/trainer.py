@@ -79,6 +79,12 @@ ring a learn samples lags the raw stores by n_step - 1 steps.  "none" (fused
 and fused=False) and "env" (with and without side_learn) run it, bit-identical
 to each other; "sample", "learn" and "full" raise ValueError for n_step > 1.
 
+A rule-based behaviour policy (AgentConfig.behavior) enters through
+agent.act_inputs(): while it is active the act's greedy actions are the
+rule's (one small launch on the stream of the act, reading the observation
+only) and its epsilon is behavior_eps.  "none" (fused and fused=False) and
+"env" run it, bit-identical to each other; the other schedules raise ValueError.
+
 Population-based training (AgentConfig.pbt): after every step the reward joins
 each replica's fitness on the caller's stream, and every `interval` steps a
 round runs there between quiesce() and join_streams(): select, the in-place
@@ -103,8 +109,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .agent import (AgentConfig, BatchedDQN, check_n_step, check_pbt, sweep_variants,
-                    variant_assignment)
+from .agent import (AgentConfig, BatchedDQN, check_behavior, check_n_step, check_pbt,
+                    sweep_variants, variant_assignment)
 from .env import EnvConfig, TrafficEnv
 
 
@@ -165,6 +171,12 @@ class Trainer:
         if check_pbt(agent_cfg, env_cfg.num_envs) is not None and overlap not in (
                 "none", "env", False):
             raise ValueError(f'pbt runs under overlap "none" or "env", not {overlap!r}')
+        # a rule-based behaviour policy (AgentConfig.behavior), checked like the
+        # two above before any device work and run under the same two schedules
+        if check_behavior(agent_cfg.behavior, agent_cfg.behavior_steps,
+                          agent_cfg.behavior_eps)[0] is not None and overlap not in (
+                "none", "env", False):
+            raise ValueError(f'behavior runs under overlap "none" or "env", not {overlap!r}')
         self.pbt_log = []  # one dict per round (_pbt_round)
         self.env = TrafficEnv(env_cfg, device=device)
         if overlap is True or overlap is False:
@@ -221,7 +233,13 @@ class Trainer:
         # a learn's output): the learn -> side-stream wait only orders the store
         # of t+2 after learn t's ring reads, so it uses ordering-only events
         # (_lib.OrderEvent, no cache write-back between the learns) from a ring
-        # (more events than marks can be alive: a wait never meets a re-record)
+        # (more events than marks can be alive: a wait never meets a re-record).
+        # "Epsilon fixed at 1" stands for "the act's greedy actions never come
+        # from the nets", and a behaviour policy (AgentConfig.behavior) keeps
+        # that true: while it is active the greedy actions are the rule's,
+        # computed on the side stream from the observation that stream itself
+        # produced, and agent.current_epsilon() -- what every condition below
+        # asks -- stays the nets' schedule, which the policy does not move.
         self._war_ring = ([_lib.OrderEvent() for _ in range(max(4, self.agent.ring.spare + 2))]
                           if war_events and overlap == "env" else None)
         self._war_i = 0

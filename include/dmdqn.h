@@ -885,6 +885,64 @@ typedef struct dmdqn_redo_args {
 } dmdqn_redo_args;
 int dmdqn_redo(const dmdqn_redo_args *args, void *stream);
 
+/* ------------------------------------------------------------------ rule-based controllers
+ * Not in the reference's code (its evaluation knows 'random' and a two-phase
+ * 'fixed' cycle, src/scripts/test.py): longest-queue-first and max-pressure,
+ * the usual baselines of signal control, as pure functions of what every agent
+ * observes.  The result is an action per agent in dmdqn_act's `greedy` format.
+ *
+ * Inputs.  obs f32 [E][A][89] as dmdqn_observe writes it; directions and
+ * approaches d = 0 n, 1 s, 2 e, 3 w (the side the vehicle comes from).
+ *     own queue          q(d,k)  = obs[3d + k]                 (lane k = 0..2)
+ *     neighbour o there  iff       obs[17 + o] == 1
+ *     its queue          nq(o,d',k') = obs[21 + 17 o + 3 d' + k']
+ * Every value is converted to int32 once (the env's observations are small
+ * integers, |v| <= 127) and all arithmetic is int32: one right answer per input.
+ *
+ * Lane groups.  Lane k of approach d belongs to action a iff the lane's primary
+ * movement (lanes 0 and 1: straight, lane 2: left) is green in phase 3a of the
+ * signal program (masks 0x11BB, 0x11DD, 0xBB11, 0xDD11, bit 4d + m with m = 0
+ * right, 1 straight, 2 left, 3 U-turn):
+ *     G0 = {n0, n1, s0, s1}   G1 = {n2, s2}   G2 = {e0, e1, w0, w1}   G3 = {e2, w2}
+ * (csrc/rule.hip derives the groups from csrc/sim.hpp's green_mask at compile
+ * time and asserts that they partition the 12 lanes).
+ *
+ * Downstream of a lane: the out-direction o of its primary movement; with the
+ * heading h = d ^ 1, straight leaves through o = h (n -> 1, s -> 0, e -> 3,
+ * w -> 2) and left through o = right_of(h) ^ 1 (n -> 2, s -> 3, e -> 1, w -> 0).
+ *     D(o) = nq(o, o ^ 1, 0) + nq(o, o ^ 1, 1) + nq(o, o ^ 1, 2)  with neighbour o,
+ *     D(o) = 0 without one (an exit edge is never "full" from here).
+ *
+ * Scores, score[a] for a = 0..3:
+ *     DMDQN_RULE_LONGEST_QUEUE   sum over (d,k) in Ga of q(d,k)
+ *     DMDQN_RULE_MAX_PRESSURE    sum over (d,k) in Ga of 3 q(d,k) - D(o(d,k))
+ * (the factor 3: the mean over the 3 downstream lanes without a division).
+ * Action: the first maximum of score[0..3], the lowest index on ties.
+ *
+ * Known answers (every obs entry not named is 0):
+ *     all zero                                   both rules: scores 0 0 0 0, action 0
+ *     obs[2] = 5 (n2)                            longest queue 0 5 0 0, max pressure
+ *                                                0 15 0 0: action 1
+ *     obs[0] = 4 (n0), obs[6] = 3 (e0),          longest queue 4 0 3 0: action 0;
+ *     obs[18] = 1, obs[38..40] = 5 5 5           max pressure -18 0 9 -15: action 2
+ *     (the neighbour to the south holds 15 on its approach from the north, where
+ *     n0 drains: the full downstream edge flips the choice).
+ *
+ * Not in this version: a minimum green or a hold (the rule is stateless: it may
+ * switch at every step); the rule as a sweep or PBT key; rules that need vehicle
+ * counts where the observation has halting counts.
+ *
+ * One 32-lane group per agent, 3 features per lane by dword loads on
+ * consecutive addresses (rows are 356 B: 4-byte aligned only), cross-lane
+ * reduction; no LDS, no atomics.  actions int32 [E*A]; score int32 [E*A][4] or
+ * NULL.  Refused on the host (DMDQN_EINVAL, nothing launched, the stream
+ * untouched): R, C or E < 1, E*R*C beyond int32, an unknown rule, obs or
+ * actions NULL. */
+#define DMDQN_RULE_LONGEST_QUEUE 0
+#define DMDQN_RULE_MAX_PRESSURE 1
+int dmdqn_act_rule(int R, int C, int E, int rule, const float *obs, int32_t *actions,
+                   int32_t *score, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,10 @@ def parse_eval_args(argv=None):
     p.add_argument("--num_eval_episodes", type=int, default=10)
     p.add_argument("--eval_seed_start", type=int, default=10000)
     p.add_argument("--eval_epsilon", type=float, default=0.01)
-    p.add_argument("--modes", nargs="+", default=["dqn", "random"])
+    p.add_argument("--modes", nargs="+", default=["dqn", "random"], choices=EV.MODES,
+                   help="the reference's dqn / random / fixed, and (not in the reference) "
+                        "longest_queue / max_pressure: the rule-based controllers; program: no "
+                        "setPhase, the net's own signal program (actuated with --actuated)")
     p.add_argument("--output_csv", default="evaluation_results.csv")
     p.add_argument("--scenario", default=DEFAULT_SCENARIO,
                    help="SUMO scenario (.sumocfg or .npz) or 'synthetic' with --grid")

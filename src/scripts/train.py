@@ -100,7 +100,8 @@ def create_agents(tl_junctions, config=AGENT_CONFIG):
 
 
 def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG, n_step=1,
-                  global_clipnorm=0.0, health_every=0, redo_every=0, redo_patience=1):
+                  global_clipnorm=0.0, health_every=0, redo_every=0, redo_patience=1,
+                  behavior=None, behavior_steps=0, behavior_eps=0.1):
     """AGENT_CONFIG with the target-network rule of --tau /
     --target_update_frequency: soft updates (dqn_agent.py:372-373, 389-399) of
     rate tau after every learn, hard syncs every target_update_frequency learns
@@ -111,8 +112,13 @@ def target_config(tau=0.0, target_update_frequency=None, config=AGENT_CONFIG, n_
     --health_every: the network health probe after every N-th learn
     (AgentConfig.health_every; 0 = off); and --redo_every / --redo_patience:
     dead-unit recycling after every N-th learn (AgentConfig.redo_every; 0 =
-    off)."""
+    off); and --behavior / --behavior_steps / --behavior_eps: a rule-based
+    behaviour policy for the first steps or the whole run (AgentConfig.behavior;
+    None = off)."""
     config = dict(config)
+    if behavior:
+        config.update(behavior=behavior, behavior_steps=int(behavior_steps),
+                      behavior_eps=float(behavior_eps))
     if redo_every:
         config["redo_every"], config["redo_patience"] = int(redo_every), int(redo_patience)
     if health_every:
@@ -222,7 +228,8 @@ def train_agents(episodes=EPISODES, rows=3, cols=3, seed=0, metrics=None, scenar
 def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, scenario=None,
                   shared=False, save_dir=None, resume=None, log_every=20, loss="mse",
                   actuated=False, tau=0.0, target_update_frequency=None, sweep=None, n_step=1,
-                  pbt=None, global_clipnorm=0.0, health_every=0, redo_every=0, redo_patience=1):
+                  pbt=None, global_clipnorm=0.0, health_every=0, redo_every=0, redo_patience=1,
+                  behavior=None, behavior_steps=0, behavior_eps=0.1):
     """E env replicas of the loop on the GPU.  The optional JSONL carries the
     reference's learn scalars (dqn_agent.py:361-370: loss, epsilon,
     q_values_mean / _std, action_distribution) and its per-step rewards with
@@ -239,7 +246,9 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
     scalars (per variant too) carry the "health" block of the last probe, and
     the final line's variants their dead_frac and update_ratio.  redo_every /
     redo_patience (AgentConfig.redo_every): each record's learn scalars carry
-    the "redo" block (rounds, the units recycled last round and in total).  pbt
+    the "redo" block (rounds, the units recycled last round and in total).
+    behavior / behavior_steps / behavior_eps (AgentConfig.behavior): every
+    record carries the "behavior" block (policy, eps, active).  pbt
     (AgentConfig.pbt, parse_pbt): population-based training; the variants then
     dissolve, so a record written at a round carries that round's pbt_log
     entry, the final line a "pbt" block (rounds, copies, the best replica of
@@ -252,7 +261,9 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
                                               global_clipnorm=global_clipnorm,
                                               health_every=health_every,
                                               redo_every=redo_every,
-                                              redo_patience=redo_patience))
+                                              redo_patience=redo_patience,
+                                              behavior=behavior, behavior_steps=behavior_steps,
+                                              behavior_eps=behavior_eps))
     cfg.precision, cfg.seed, cfg.shared_params, cfg.loss = precision, seed, shared, loss
     cfg.sweep, cfg.pbt = sweep, pbt
     tr = Trainer(EnvConfig(rows=rows, cols=cols, num_envs=envs, seed=seed, scenario=scenario,
@@ -287,6 +298,8 @@ def train_batched(episodes, rows, cols, envs, precision, seed, metrics=None, sce
                    "smooth_total_reward": smooth_total.get_value()}
             if st.loss_launched:
                 rec.update(tr.agent.learn_metrics())
+            if tr.agent.behavior is not None:  # (before the first learn too)
+                rec["behavior"] = tr.agent.behavior_metrics()
             if variants:
                 if st.loss_launched:
                     vrec = tr.agent.learn_metrics(by_variant=True)
@@ -439,12 +452,23 @@ def main():
     ap.add_argument("--redo_patience", type=int, default=1, metavar="K",
                     help="with --redo_every: a unit is recycled once it was dead on K probes in "
                          "a row (1..255)")
+    ap.add_argument("--behavior", default=None, choices=["longest_queue", "max_pressure"],
+                    help="batched only: a rule-based behaviour policy -- while it is active the "
+                         "agents take the controller's action (a uniform one below "
+                         "--behavior_eps) instead of epsilon-greedy on their nets, so the "
+                         "replay fills with a controller's transitions; the metrics gain a "
+                         "\"behavior\" block.  Default: off")
+    ap.add_argument("--behavior_steps", type=int, default=0, metavar="N",
+                    help="with --behavior: active for the first N env steps (0 = the whole run)")
+    ap.add_argument("--behavior_eps", type=float, default=0.1, metavar="F",
+                    help="with --behavior: the share of uniformly random actions, in [0, 1]")
     args = ap.parse_args()
     try:
         sweep = parse_sweep(args.sweep)
         pbt = parse_pbt(args.pbt, args.pbt_perturb)
-        from dmdqn_amd.agent import (check_clipnorm, check_health_every, check_n_step,
-                                     check_redo)
+        from dmdqn_amd.agent import (check_behavior, check_clipnorm, check_health_every,
+                                     check_n_step, check_redo)
+        check_behavior(args.behavior, args.behavior_steps, args.behavior_eps)
         check_health_every(args.health_every)
         check_redo(args.redo_every, args.redo_patience)
         check_n_step(args.n_step, AGENT_CONFIG["replay_buffer_size"])
@@ -467,6 +491,8 @@ def main():
         ap.error("--redo_every needs --batched")
     if args.redo_every and (args.shared or args.precision == "fp32"):
         ap.error("--redo_every runs with --precision fp16 / bf16, not with --shared")
+    if args.behavior and not args.batched:
+        ap.error("--behavior needs --batched")
     logging.basicConfig(level=logging.INFO)
     rows, cols = (int(x) for x in args.grid.split("x"))
     scenario = args.scenario
@@ -479,7 +505,7 @@ def main():
                       scenario, args.shared, args.save_dir, args.resume, args.log_every, args.loss,
                       args.actuated, args.tau, args.target_update_frequency, sweep, args.n_step,
                       pbt, args.global_clipnorm, args.health_every, args.redo_every,
-                      args.redo_patience)
+                      args.redo_patience, args.behavior, args.behavior_steps, args.behavior_eps)
     else:
         train_agents(args.episodes, rows, cols, args.seed, args.metrics, scenario, args.save_dir,
                      args.tau, args.target_update_frequency, args.n_step)
