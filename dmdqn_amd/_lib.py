@@ -17,7 +17,7 @@ _SUFFIX = f"_{VARIANT}" if VARIANT else ""
 LIB_PATH = os.path.join(_HERE, "lib", f"libdmdqn_hip{_SUFFIX}.so")
 _LIB = None
 
-vp, i32, u32, u64, f64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_double
+vp, i32, u32, u64, f32, f64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_double
 
 # name -> argtypes (all return int status)
 SIGNATURES = {
@@ -59,9 +59,51 @@ class DmdqnError(RuntimeError):
 NSTEP_MAX = 32  # include/dmdqn.h DMDQN_NSTEP_MAX
 
 
+class CLearn(C.Structure):
+    """include/dmdqn.h dmdqn_learn_args."""
+    _fields_ = [(n, C.c_int32) for n in ["NA", "cap", "start", "batch", "hidden", "precision",
+                                         "sync_target", "P"]] + [
+        (n, C.c_void_p) for n in ["ring_s", "ring_n", "ring_a", "ring_d", "ring_r", "idx",
+                                  "params", "adam_m", "adam_v", "target", "target_h",
+                                  "loss"]] + [
+        (n, C.c_float) for n in ["gamma", "alpha", "c1", "c2", "eps"]] + [
+        ("stamps", C.c_void_p), ("qstats", C.c_void_p), ("params_h", C.c_void_p),
+        ("loss_kind", C.c_int32), ("rn_out", C.c_void_p), ("row_format", C.c_int32),
+        ("xs", C.c_void_p), ("xn", C.c_void_p), ("tau", C.c_float), ("one_minus_tau", C.c_float)]
+
+
+class CHParams(C.Structure):
+    """include/dmdqn.h dmdqn_agent_hparams."""
+    _fields_ = [(n, C.c_void_p) for n in ["lr", "gamma", "tau", "one_minus_tau"]] + [
+        ("adam_s", C.c_float), ("adam_d", C.c_float)]
+
+
+# the learn entry points: the C-ABI tests call them directly (BatchedDQN.c_learn_args);
+# the product path goes through torch.ops.dmdqn
+_pl, _ph = C.POINTER(CLearn), C.POINTER(CHParams)
+SIGNATURES.update({
+    "dmdqn_learn": [_pl, vp],
+    "dmdqn_learn_grad": [_pl, vp, vp],
+    "dmdqn_adam_agents": [_pl, vp, vp],
+    "dmdqn_learn_hp": [_pl, _ph, vp],
+    "dmdqn_learn_grad_hp": [_pl, _ph, vp, vp],
+    "dmdqn_adam_agents_hp": [_pl, _ph, vp, vp],
+    "dmdqn_adam_agents_clip": [_pl, _ph, vp, f32, vp, vp],
+    "dmdqn_learn_pair": [_pl, _pl, _ph, _ph, vp],
+    "dmdqn_learn_shared_grad": [_pl, vp, i32, vp, f32, vp, vp],
+    "dmdqn_adam": [vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, i32, vp],
+    "dmdqn_adam_slabs": [vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, i32, f32, f32, f32, f32, f32,
+                         i32, vp],
+    "dmdqn_target_sync": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "dmdqn_target_soft_update": [vp, vp, vp, i32, i32, i32, i32, f32, f32, vp],
+    "dmdqn_target_soft_update_hp": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "dmdqn_q_argmax": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
+    "dmdqn_q_argmax_shared": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
+})
+
+
 class CNStep(C.Structure):
-    """include/dmdqn.h dmdqn_nstep_args (agent.CLearn / CHParams mirror the
-    learn's structs)."""
+    """include/dmdqn.h dmdqn_nstep_args."""
     _fields_ = [(n, C.c_int32) for n in ["NA", "n", "head", "cap", "slot", "row_format"]] + [
         (n, C.c_void_p) for n in ["st_s", "st_n", "st_a", "st_r", "st_d", "ring_s", "ring_n",
                                   "ring_a", "ring_r", "ring_d"]] + [
@@ -79,7 +121,7 @@ class CProbe(C.Structure):
 
 
 SIGNATURES["dmdqn_net_probe"] = [C.POINTER(CProbe), vp]
-SIGNATURES["dmdqn_layer_norms"] = [vp, vp, C.c_float, i32, i32, i32, i32, vp, vp]
+SIGNATURES["dmdqn_layer_norms"] = [vp, vp, f32, i32, i32, i32, i32, vp, vp]
 
 
 class CRedo(C.Structure):
@@ -91,14 +133,6 @@ class CRedo(C.Structure):
 
 
 SIGNATURES["dmdqn_redo"] = [C.POINTER(CRedo), vp]
-
-
-def register(sigs):
-    """Add entry-point signatures (modules that define the ctypes structs call
-    this); applied at once if the library is already loaded."""
-    SIGNATURES.update(sigs)
-    if _LIB is not None:
-        _apply(_LIB, sigs)
 
 
 def _apply(lib, sigs):

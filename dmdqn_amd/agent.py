@@ -52,7 +52,6 @@ weights and zero Adam moments (ReDo; include/dmdqn.h dmdqn_redo).  With
 AgentConfig.redo_every = N a Trainer calls it after every N-th learn and
 learn_metrics() reports the rounds under "redo".
 """
-import ctypes as C
 import itertools
 import math
 from dataclasses import dataclass, field
@@ -69,56 +68,8 @@ D_IN = 89
 N_ACTIONS = 4
 
 
-class CLearn(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ["NA", "cap", "start", "batch", "hidden", "precision",
-                                         "sync_target", "P"]] + [
-        (n, C.c_void_p) for n in ["ring_s", "ring_n", "ring_a", "ring_d", "ring_r", "idx",
-                                  "params", "adam_m", "adam_v", "target", "target_h",
-                                  "loss"]] + [
-        (n, C.c_float) for n in ["gamma", "alpha", "c1", "c2", "eps"]] + [
-        ("stamps", C.c_void_p), ("qstats", C.c_void_p), ("params_h", C.c_void_p),
-        ("loss_kind", C.c_int32), ("rn_out", C.c_void_p), ("row_format", C.c_int32),
-        ("xs", C.c_void_p), ("xn", C.c_void_p), ("tau", C.c_float), ("one_minus_tau", C.c_float)]
-
-
-class CHParams(C.Structure):
-    """include/dmdqn.h dmdqn_agent_hparams."""
-    _fields_ = [(n, C.c_void_p) for n in ["lr", "gamma", "tau", "one_minus_tau"]] + [
-        ("adam_s", C.c_float), ("adam_d", C.c_float)]
-
-
-# ctypes signatures of the learn entry points: the C-ABI tests call them
-# directly (c_learn_args); the product path goes through torch.ops.dmdqn
-_lib.register({
-    "dmdqn_learn": [C.POINTER(CLearn), C.c_void_p],
-    "dmdqn_learn_grad": [C.POINTER(CLearn), C.c_void_p, C.c_void_p],
-    "dmdqn_adam_agents": [C.POINTER(CLearn), C.c_void_p, C.c_void_p],
-    "dmdqn_q_argmax": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                       C.c_void_p, C.c_void_p],
-    "dmdqn_q_argmax_shared": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                              C.c_void_p, C.c_void_p, C.c_void_p],
-    "dmdqn_learn_shared_grad": [C.POINTER(CLearn), C.c_void_p, C.c_int, C.c_void_p, C.c_float,
-                                C.c_void_p, C.c_void_p],
-    "dmdqn_adam": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                   C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                   C.c_int, C.c_void_p],
-    "dmdqn_adam_slabs": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                         C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_float, C.c_float,
-                         C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p],
-    "dmdqn_target_sync": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                          C.c_void_p],
-    "dmdqn_target_soft_update": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                 C.c_int, C.c_float, C.c_float, C.c_void_p],
-    "dmdqn_learn_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p],
-    "dmdqn_learn_grad_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_void_p],
-    "dmdqn_adam_agents_hp": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_void_p],
-    "dmdqn_adam_agents_clip": [C.POINTER(CLearn), C.POINTER(CHParams), C.c_void_p, C.c_float,
-                               C.c_void_p, C.c_void_p],
-    "dmdqn_learn_pair": [C.POINTER(CLearn), C.POINTER(CLearn), C.POINTER(CHParams),
-                         C.POINTER(CHParams), C.c_void_p],
-    "dmdqn_target_soft_update_hp": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
-})
+CLearn = _lib.CLearn  # include/dmdqn.h dmdqn_learn_args
+CHParams = _lib.CHParams  # include/dmdqn.h dmdqn_agent_hparams
 
 PRECISIONS = {"fp32": 0, "fp16": 1, "bf16": 2}
 # include/dmdqn.h DMDQN_LOSS_*: the reference's MSE (dqn_agent.py:352) and the
@@ -1255,6 +1206,17 @@ class BatchedDQN:
             next_sync=cfg.target_update_frequency > 0 and nxt % cfg.target_update_frequency == 0)
         return self._last_tok
 
+    @staticmethod
+    def _slice(lo, hi):
+        """t -> the rows of agents [lo, hi) of a per-agent tensor (None stays None)."""
+        return lambda t: None if t is None else t[lo:hi]
+
+    def _hp_kwargs(self, sl):
+        """The per-agent hyperparameter arrays of an agent range (its _slice),
+        under the operators' keyword names; None where a key is not swept."""
+        return dict(lr=sl(self.hp_lr), gamma_a=sl(self.hp_gamma), tau_a=sl(self.hp_tau),
+                    one_minus_tau_a=sl(self.hp_omt))
+
     def learn_range(self, lo, hi, tok=None):
         """Launch the learn begun by learn_begin() -- the last one, or the one
         whose token is given -- for agents [lo, hi) on the current stream (the
@@ -1284,9 +1246,7 @@ class BatchedDQN:
                     self._xn = torch.empty(shape, dtype=torch.float32, device=self.device)
                 ring.gather_f32(tok.idx, self._xs, self._xn)
                 xs, xn = self._xs, self._xn
-
-            def sl(t):
-                return None if t is None else t[lo:hi]
+            sl = self._slice(lo, hi)
             args = (sl(ring.s), sl(ring.n), sl(ring.a), sl(ring.d), sl(ring.r),
                     sl(tok.idx), sl(self.params), sl(self.adam_m), sl(self.adam_v),
                     sl(self.target), sl(self.target_h), sl(tok.loss), tok.start,
@@ -1294,19 +1254,14 @@ class BatchedDQN:
                     eps, LOSSES[cfg.loss], sl(qstats), sl(self.rn_out), sl(self.stamps))
             kw = dict(grad=sl(self._split_grad), xs=xs, xn=xn, tau=float(tau_f),
                       one_minus_tau=float(omt_f))
+            op = "learn_step"
+            if self.clipnorm > 0 or self.swept:  # the per-agent arrays and this learn's factors
+                op = "learn_step_hp"
+                kw.update(self._hp_kwargs(sl), adam_s=tok.factors[0], adam_d=tok.factors[1])
             if self.clipnorm > 0:  # the split learn with the clipping Adam launch
-                s, d = tok.factors
-                self._ops.learn_step_clip(*args, **kw, lr=sl(self.hp_lr), gamma_a=sl(self.hp_gamma),
-                                          tau_a=sl(self.hp_tau), one_minus_tau_a=sl(self.hp_omt),
-                                          adam_s=s, adam_d=d, clip=self.clipnorm,
-                                          gnorm=sl(tok.gnorm))
-            elif self.swept:  # the range's slice of the per-agent arrays, like every tensor
-                s, d = tok.factors
-                self._ops.learn_step_hp(*args, **kw, lr=sl(self.hp_lr), gamma_a=sl(self.hp_gamma),
-                                        tau_a=sl(self.hp_tau), one_minus_tau_a=sl(self.hp_omt),
-                                        adam_s=s, adam_d=d)
-            else:
-                self._ops.learn_step(*args, **kw)
+                op = "learn_step_clip"
+                kw.update(clip=self.clipnorm, gnorm=sl(tok.gnorm))
+            getattr(self._ops, op)(*args, **kw)
         if hook:
             hook(False)
         return tok.loss
@@ -1334,17 +1289,14 @@ class BatchedDQN:
         for t in (tok0, tok1):
             if t.qstats is not None:
                 t.qstats[lo:hi].zero_()  # the kernels accumulate into it
-
-        def sl(t):
-            return None if t is None else t[lo:hi]
+        sl = self._slice(lo, hi)
         self._ops.learn_pair(
             sl(ring.s), sl(ring.n), sl(ring.a), sl(ring.d), sl(ring.r), sl(self.params),
             sl(self.adam_m), sl(self.adam_v), sl(self.target), sl(self.target_h), sl(tok0.idx),
             sl(tok1.idx), sl(tok0.loss), sl(tok1.loss), tok0.start, tok1.start, self.H,
             PRECISIONS[cfg.precision], self.gamma_n, list(tok0.adam), list(tok1.adam),
             LOSSES[cfg.loss], qstats0=sl(tok0.qstats), qstats1=sl(tok1.qstats),
-            tau=float(tau_f), one_minus_tau=float(omt_f), lr=sl(self.hp_lr),
-            gamma_a=sl(self.hp_gamma), tau_a=sl(self.hp_tau), one_minus_tau_a=sl(self.hp_omt),
+            tau=float(tau_f), one_minus_tau=float(omt_f), **self._hp_kwargs(sl),
             factors0=list(tok0.factors), factors1=list(tok1.factors))
         if lo == 0:
             self.pair_launches += 1

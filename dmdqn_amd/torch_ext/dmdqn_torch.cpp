@@ -67,6 +67,83 @@ int int32_of(int64_t v, const char *name) {
 
 constexpr int64_t MT = DMDQN_MT_WORDS;
 
+// ---------------------------------------------------------------- shared checks
+// every tensor of ts (nullptr: an absent optional, see opt()) on the device of ref
+void same_device(const Tensor &ref, std::initializer_list<const Tensor *> ts, const char *msg) {
+    for (const Tensor *t : ts) TORCH_CHECK(t == nullptr || t->device() == ref.device(), msg);
+}
+
+const Tensor *opt(const OptT &t) { return t.has_value() ? &*t : nullptr; }
+
+// the two sizes of a [rows, cols] tensor
+std::pair<int64_t, int64_t> dims2(const Tensor &t, const char *msg) {
+    TORCH_CHECK(t.dim() == 2, msg);
+    return {t.size(0), t.size(1)};
+}
+
+// err: one int32 in a device tensor, or in pinned host memory the kernel writes directly
+int32_t *err_ptr(Tensor &err) {
+    TORCH_CHECK(err.is_cuda() || err.is_pinned(), "err must be a device tensor or pinned host memory");
+    TORCH_CHECK(err.scalar_type() == at::kInt && err.numel() == 1, "err must be one int32");
+    return reinterpret_cast<int32_t *>(err.data_ptr());
+}
+
+dmdqn_idm make_idm(at::ArrayRef<double> idm) {
+    TORCH_CHECK(idm.size() == 12, "idm: 12 constants (include/dmdqn.h dmdqn_idm order)");
+    return dmdqn_idm{(float)idm[0], (float)idm[1], (float)idm[2], (float)idm[3],
+                     (float)idm[4], (float)idm[5], (float)idm[6], (float)idm[7],
+                     (float)idm[8], (float)idm[9], (float)idm[10], (float)idm[11]};
+}
+
+// The five arrays of a replay ring of NA agents x cap slots.  rows: at::kChar
+// (DMDQN_ROW_BYTES per row) or at::kFloat (DMDQN_ROW_FLOATS); Undefined: the
+// caller does not read the rows (s, n stay null and unchecked).
+struct Rings {
+    void *s, *n;
+    uint8_t *a, *d;
+    double *r;
+};
+
+int64_t ring_cap(const Tensor &ring_a, int64_t NA) {
+    TORCH_CHECK(NA > 0 && ring_a.numel() % NA == 0, "ring_a must be [NA, cap]");
+    return ring_a.numel() / NA;
+}
+
+Rings ring_ptrs(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
+                const Tensor &ring_r, const Tensor &ring_d, int64_t NA, int64_t cap,
+                at::ScalarType rows, const char *s_name = "ring_s",
+                const char *n_name = "ring_n") {
+    Rings g{};
+    if (rows != at::ScalarType::Undefined) {
+        const int64_t row = rows == at::kFloat ? DMDQN_ROW_FLOATS : DMDQN_ROW_BYTES;
+        g.s = dptr<void>(ring_s, rows, s_name, NA * cap * row);
+        g.n = dptr<void>(ring_n, rows, n_name, NA * cap * row);
+    }
+    g.a = dptr<uint8_t>(ring_a, at::kByte, "ring_a", NA * cap);
+    g.r = dptr<double>(ring_r, at::kDouble, "ring_r", NA * cap);
+    g.d = dptr<uint8_t>(ring_d, at::kByte, "ring_d", NA * cap);
+    return g;
+}
+
+// One transition per agent as the env hands it over (the input of both stores).
+struct Stored {
+    const float *s, *n;
+    const int32_t *a;
+    const double *r;
+    const uint8_t *d;
+};
+
+Stored stored_ptrs(const Tensor &obs_s, const Tensor &obs_n, const Tensor &act_, const Tensor &rew,
+                   const Tensor &done, int64_t NA) {
+    Stored t{};
+    t.s = dptr<float>(obs_s, at::kFloat, "obs_s", NA * DMDQN_OBS_DIM);
+    t.n = dptr<float>(obs_n, at::kFloat, "obs_n", NA * DMDQN_OBS_DIM);
+    t.a = dptr<int32_t>(act_, at::kInt, "act", NA);
+    t.r = dptr<double>(rew, at::kDouble, "rew", NA);
+    t.d = dptr<uint8_t>(done, at::kByte, "done", NA);
+    return t;
+}
+
 // ---------------------------------------------------------------- streams / act
 void mt_seed(Tensor &state, const Tensor &seeds, const std::string &kind) {
     const int64_t E = seeds.numel();
@@ -130,48 +207,28 @@ void observe(int64_t R, int64_t C, const Tensor &halt, const Tensor &phase, cons
 void replay_store(int64_t slot, const Tensor &obs_s, const Tensor &obs_n, const Tensor &act_,
                   const Tensor &rew, const Tensor &done, Tensor &ring_s, Tensor &ring_n,
                   Tensor &ring_a, Tensor &ring_r, Tensor &ring_d, Tensor &err) {
-    const int64_t NA = act_.numel();
-    TORCH_CHECK(NA > 0 && ring_a.numel() % NA == 0, "ring_a must be [NA, cap]");
-    const int64_t cap = ring_a.numel() / NA;
-    auto s = dptr<float>(obs_s, at::kFloat, "obs_s", NA * DMDQN_OBS_DIM);
-    auto n = dptr<float>(obs_n, at::kFloat, "obs_n", NA * DMDQN_OBS_DIM);
-    auto a = dptr<int32_t>(act_, at::kInt, "act");
-    auto r = dptr<double>(rew, at::kDouble, "rew", NA);
-    auto d = dptr<uint8_t>(done, at::kByte, "done", NA);
-    auto rs = dptr<int8_t>(ring_s, at::kChar, "ring_s", NA * cap * DMDQN_ROW_BYTES);
-    auto rn = dptr<int8_t>(ring_n, at::kChar, "ring_n", NA * cap * DMDQN_ROW_BYTES);
-    auto ra = dptr<uint8_t>(ring_a, at::kByte, "ring_a", NA * cap);
-    auto rr = dptr<double>(ring_r, at::kDouble, "ring_r", NA * cap);
-    auto rd = dptr<uint8_t>(ring_d, at::kByte, "ring_d", NA * cap);
-    // err: a device tensor, or pinned host memory the kernel writes directly
-    TORCH_CHECK(err.is_cuda() || err.is_pinned(), "err must be a device tensor or pinned host memory");
-    TORCH_CHECK(err.scalar_type() == at::kInt && err.numel() == 1, "err must be one int32");
-    auto e = reinterpret_cast<int32_t *>(err.data_ptr());
+    const int64_t NA = act_.numel(), cap = ring_cap(ring_a, NA);
+    const Stored t = stored_ptrs(obs_s, obs_n, act_, rew, done, NA);
+    const Rings rg = ring_ptrs(ring_s, ring_n, ring_a, ring_r, ring_d, NA, cap, at::kChar);
+    auto e = err_ptr(err);
     c10::hip::HIPGuardMasqueradingAsCUDA g(obs_s.device());
-    check(dmdqn_replay_store((int)NA, int32_of(cap, "cap"), int32_of(slot, "slot"), s, n, a, r, d,
-                             rs, rn, ra, rr, rd, e, stream_of(obs_s)),
+    check(dmdqn_replay_store((int)NA, int32_of(cap, "cap"), int32_of(slot, "slot"), t.s, t.n, t.a,
+                             t.r, t.d, (int8_t *)rg.s, (int8_t *)rg.n, rg.a, rg.r, rg.d, e,
+                             stream_of(obs_s)),
           "dmdqn_replay_store");
 }
 
 void replay_store_f32(int64_t slot, const Tensor &obs_s, const Tensor &obs_n, const Tensor &act_,
                       const Tensor &rew, const Tensor &done, Tensor &rows_s, Tensor &rows_n,
                       Tensor &ring_a, Tensor &ring_r, Tensor &ring_d) {
-    const int64_t NA = act_.numel();
-    TORCH_CHECK(NA > 0 && ring_a.numel() % NA == 0, "ring_a must be [NA, cap]");
-    const int64_t cap = ring_a.numel() / NA;
-    auto s = dptr<float>(obs_s, at::kFloat, "obs_s", NA * DMDQN_OBS_DIM);
-    auto n = dptr<float>(obs_n, at::kFloat, "obs_n", NA * DMDQN_OBS_DIM);
-    auto a = dptr<int32_t>(act_, at::kInt, "act", NA);
-    auto r = dptr<double>(rew, at::kDouble, "rew", NA);
-    auto d = dptr<uint8_t>(done, at::kByte, "done", NA);
-    auto rs = dptr<float>(rows_s, at::kFloat, "rows_s", NA * cap * DMDQN_ROW_FLOATS);
-    auto rn = dptr<float>(rows_n, at::kFloat, "rows_n", NA * cap * DMDQN_ROW_FLOATS);
-    auto ra = dptr<uint8_t>(ring_a, at::kByte, "ring_a", NA * cap);
-    auto rr = dptr<double>(ring_r, at::kDouble, "ring_r", NA * cap);
-    auto rd = dptr<uint8_t>(ring_d, at::kByte, "ring_d", NA * cap);
+    const int64_t NA = act_.numel(), cap = ring_cap(ring_a, NA);
+    const Stored t = stored_ptrs(obs_s, obs_n, act_, rew, done, NA);
+    const Rings rg = ring_ptrs(rows_s, rows_n, ring_a, ring_r, ring_d, NA, cap, at::kFloat,
+                               "rows_s", "rows_n");
     c10::hip::HIPGuardMasqueradingAsCUDA g(obs_s.device());
-    check(dmdqn_replay_store_f32((int)NA, int32_of(cap, "cap"), int32_of(slot, "slot"), s, n, a, r,
-                                 d, rs, rn, ra, rr, rd, stream_of(obs_s)),
+    check(dmdqn_replay_store_f32((int)NA, int32_of(cap, "cap"), int32_of(slot, "slot"), t.s, t.n,
+                                 t.a, t.r, t.d, (float *)rg.s, (float *)rg.n, rg.a, rg.r, rg.d,
+                                 stream_of(obs_s)),
           "dmdqn_replay_store_f32");
 }
 
@@ -218,18 +275,13 @@ void replay_nstep_commit(int64_t head, int64_t slot, const Tensor &st_s, const T
     a.st_a = dptr<uint8_t>(st_a, at::kByte, "st_a", NA * n);
     a.st_r = dptr<double>(st_r, at::kDouble, "st_r", NA * n);
     a.st_d = dptr<uint8_t>(st_d, at::kByte, "st_d", NA * n);
-    a.ring_s = dptr<void>(ring_s, rt, "ring_s", NA * cap * rw);
-    a.ring_n = dptr<void>(ring_n, rt, "ring_n", NA * cap * rw);
-    a.ring_a = dptr<uint8_t>(ring_a, at::kByte, "ring_a", NA * cap);
-    a.ring_r = dptr<double>(ring_r, at::kDouble, "ring_r", NA * cap);
-    a.ring_d = dptr<uint8_t>(ring_d, at::kByte, "ring_d", NA * cap);
+    const Rings rg = ring_ptrs(ring_s, ring_n, ring_a, ring_r, ring_d, NA, cap, rt);
+    a.ring_s = rg.s; a.ring_n = rg.n; a.ring_a = rg.a; a.ring_r = rg.r; a.ring_d = rg.d;
     a.gamma = gamma;
     a.gamma_a = optr<const double>(gamma_a, at::kDouble, "gamma_a", NA);
-    for (const Tensor *t : std::initializer_list<const Tensor *>{
-             &st_n, &st_a, &st_r, &st_d, &ring_s, &ring_n, &ring_a, &ring_r, &ring_d})
-        TORCH_CHECK(t->device() == st_s.device(), "staging and replay rings must share a device");
-    TORCH_CHECK(!gamma_a.has_value() || gamma_a->device() == st_s.device(),
-                "gamma_a must be on the device of the rings");
+    same_device(st_s, {&st_n, &st_a, &st_r, &st_d, &ring_s, &ring_n, &ring_a, &ring_r, &ring_d},
+                "staging and replay rings must share a device");
+    same_device(st_s, {opt(gamma_a)}, "gamma_a must be on the device of the rings");
     c10::hip::HIPGuardMasqueradingAsCUDA g(st_s.device());
     check(dmdqn_replay_nstep_commit(&a, stream_of(st_s)), "dmdqn_replay_nstep_commit");
 }
@@ -290,23 +342,33 @@ void sim_reset(at::TensorList state, at::TensorList tables, at::IntArrayRef dims
     check(dmdqn_sim_reset_envs(&s, m, stream_of(state[0])), "dmdqn_sim_reset_envs");
 }
 
+// what a step of E envs x A junctions writes for the observation that follows
+struct StepOut {
+    int32_t *halt, *phase, *tspent;
+    uint8_t *done;
+};
+
+StepOut step_out(Tensor &halt, Tensor &phase, Tensor &tspent, Tensor &done, int64_t E, int64_t A) {
+    StepOut o{};
+    o.halt = dptr<int32_t>(halt, at::kInt, "halt", E * A * 12);
+    o.phase = dptr<int32_t>(phase, at::kInt, "phase", E * A);
+    o.tspent = dptr<int32_t>(tspent, at::kInt, "tspent", E * A);
+    o.done = dptr<uint8_t>(done, at::kByte, "done", E);
+    return o;
+}
+
 void sim_step(at::TensorList state, at::TensorList tables, at::IntArrayRef dims,
               at::ArrayRef<double> idm, const OptT &actions, int64_t stride, int64_t t0, int64_t K,
               int64_t max_time, Tensor &halt, Tensor &phase, Tensor &tspent, Tensor &done) {
     dmdqn_sim s = make_sim(state, tables, dims);
-    TORCH_CHECK(idm.size() == 12, "idm: 12 constants (include/dmdqn.h dmdqn_idm order)");
-    dmdqn_idm p{(float)idm[0], (float)idm[1], (float)idm[2], (float)idm[3], (float)idm[4],
-                (float)idm[5], (float)idm[6], (float)idm[7], (float)idm[8], (float)idm[9],
-                (float)idm[10], (float)idm[11]};
+    dmdqn_idm p = make_idm(idm);
     const int64_t A = (int64_t)s.R * s.C, E = s.E;
     auto a = optr<int32_t>(actions, at::kInt, "actions", E * A);
-    auto h = dptr<int32_t>(halt, at::kInt, "halt", E * A * 12);
-    auto ph = dptr<int32_t>(phase, at::kInt, "phase", E * A);
-    auto ts = dptr<int32_t>(tspent, at::kInt, "tspent", E * A);
-    auto d = dptr<uint8_t>(done, at::kByte, "done", E);
+    const StepOut o = step_out(halt, phase, tspent, done, E, A);
     c10::hip::HIPGuardMasqueradingAsCUDA g(halt.device());
     check(dmdqn_sim_step(&s, &p, a, (int)stride, int32_of(t0, "t0"), (int)K,
-                         int32_of(max_time, "max_time"), h, ph, ts, d, stream_of(halt)),
+                         int32_of(max_time, "max_time"), o.halt, o.phase, o.tspent, o.done,
+                         stream_of(halt)),
           "dmdqn_sim_step");
 }
 
@@ -319,15 +381,9 @@ void env_step(at::TensorList state, at::TensorList tables, at::IntArrayRef dims,
               const Tensor &obs_s, int64_t slot, Tensor &ring_s, Tensor &ring_n, Tensor &ring_a,
               Tensor &ring_r, Tensor &ring_d, Tensor &err) {
     dmdqn_sim s = make_sim(state, tables, dims);
-    TORCH_CHECK(idm.size() == 12, "idm: 12 constants (include/dmdqn.h dmdqn_idm order)");
-    dmdqn_idm p{(float)idm[0], (float)idm[1], (float)idm[2], (float)idm[3], (float)idm[4],
-                (float)idm[5], (float)idm[6], (float)idm[7], (float)idm[8], (float)idm[9],
-                (float)idm[10], (float)idm[11]};
+    dmdqn_idm p = make_idm(idm);
     const int64_t A = (int64_t)s.R * s.C, E = s.E, NA = E * A;
-    auto h = dptr<int32_t>(halt, at::kInt, "halt", E * A * 12);
-    auto ph = dptr<int32_t>(phase, at::kInt, "phase", E * A);
-    auto ts = dptr<int32_t>(tspent, at::kInt, "tspent", E * A);
-    auto d = dptr<uint8_t>(done, at::kByte, "done", E);
+    const StepOut o = step_out(halt, phase, tspent, done, E, A);
     TORCH_CHECK(ring_a.numel() % NA == 0 && ring_a.numel() > 0, "ring_a must be [E*A, cap]");
     const int64_t cap = ring_a.numel() / NA;
     dmdqn_env_fuse f{};
@@ -344,17 +400,14 @@ void env_step(at::TensorList state, at::TensorList tables, at::IntArrayRef dims,
     f.obs_s = dptr<float>(obs_s, at::kFloat, "obs_s", NA * DMDQN_OBS_DIM);
     f.cap = int32_of(cap, "cap");
     f.slot = int32_of(slot, "slot");
-    f.ring_s = dptr<int8_t>(ring_s, at::kChar, "ring_s", NA * cap * DMDQN_ROW_BYTES);
-    f.ring_n = dptr<int8_t>(ring_n, at::kChar, "ring_n", NA * cap * DMDQN_ROW_BYTES);
-    f.ring_a = dptr<uint8_t>(ring_a, at::kByte, "ring_a", NA * cap);
-    f.ring_r = dptr<double>(ring_r, at::kDouble, "ring_r", NA * cap);
-    f.ring_d = dptr<uint8_t>(ring_d, at::kByte, "ring_d", NA * cap);
-    TORCH_CHECK(err.is_cuda() || err.is_pinned(), "err must be a device tensor or pinned host memory");
-    TORCH_CHECK(err.scalar_type() == at::kInt && err.numel() == 1, "err must be one int32");
-    f.err = reinterpret_cast<int32_t *>(err.data_ptr());
+    const Rings rg = ring_ptrs(ring_s, ring_n, ring_a, ring_r, ring_d, NA, cap, at::kChar);
+    f.ring_s = (int8_t *)rg.s; f.ring_n = (int8_t *)rg.n;
+    f.ring_a = rg.a; f.ring_r = rg.r; f.ring_d = rg.d;
+    f.err = err_ptr(err);
     c10::hip::HIPGuardMasqueradingAsCUDA g(halt.device());
     check(dmdqn_env_step(&s, &p, &f, (int)stride, int32_of(t0, "t0"), (int)K,
-                         int32_of(max_time, "max_time"), h, ph, ts, d, stream_of(halt)),
+                         int32_of(max_time, "max_time"), o.halt, o.phase, o.tspent, o.done,
+                         stream_of(halt)),
           "dmdqn_env_step");
 }
 
@@ -369,8 +422,7 @@ dmdqn_learn_args make_learn(const Tensor &ring_s, const Tensor &ring_n, const Te
                             const OptT &stamps, int64_t NA, int64_t NW,
                             const OptT &xs = std::nullopt, const OptT &xn = std::nullopt) {
     dmdqn_learn_args a{};
-    TORCH_CHECK(NA > 0 && ring_a.numel() % NA == 0, "ring_a must be [NA, cap]");
-    const int64_t cap = ring_a.numel() / NA, B = idx.numel() / NA;
+    const int64_t cap = ring_cap(ring_a, NA), B = idx.numel() / NA;
     TORCH_CHECK(NW > 0 && params.numel() % NW == 0, "params must be [NW, P]");
     const int64_t P = params.numel() / NW;
     a.NA = (int)NA; a.cap = int32_of(cap, "cap"); a.start = int32_of(start, "start");
@@ -381,13 +433,11 @@ dmdqn_learn_args make_learn(const Tensor &ring_s, const Tensor &ring_n, const Te
         a.row_format = DMDQN_ROWS_F32;
         a.xs = dptr<float>(*xs, at::kFloat, "xs", NA * B * DMDQN_ROW_FLOATS);
         a.xn = dptr<float>(*xn, at::kFloat, "xn", NA * B * DMDQN_ROW_FLOATS);
-    } else {
-        a.ring_s = dptr<int8_t>(ring_s, at::kChar, "ring_s", NA * cap * DMDQN_ROW_BYTES);
-        a.ring_n = dptr<int8_t>(ring_n, at::kChar, "ring_n", NA * cap * DMDQN_ROW_BYTES);
     }
-    a.ring_a = dptr<uint8_t>(ring_a, at::kByte, "ring_a", NA * cap);
-    a.ring_d = dptr<uint8_t>(ring_d, at::kByte, "ring_d", NA * cap);
-    a.ring_r = dptr<double>(ring_r, at::kDouble, "ring_r", NA * cap);
+    const Rings rg = ring_ptrs(ring_s, ring_n, ring_a, ring_r, ring_d, NA, cap,
+                               xs.has_value() ? at::ScalarType::Undefined : at::kChar);
+    a.ring_s = (const int8_t *)rg.s; a.ring_n = (const int8_t *)rg.n;
+    a.ring_a = rg.a; a.ring_d = rg.d; a.ring_r = rg.r;
     a.idx = dptr<int32_t>(idx, at::kInt, "idx", NA * B);
     a.params = dptr<float>(params, at::kFloat, "params");
     a.adam_m = optr<float>(adam_m, at::kFloat, "adam_m", NW * P);
@@ -408,13 +458,43 @@ dmdqn_learn_args make_learn(const Tensor &ring_s, const Tensor &ring_n, const Te
     return a;
 }
 
-void learn_step(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
-                const Tensor &ring_d, const Tensor &ring_r, const Tensor &idx, Tensor &params,
-                Tensor &adam_m, Tensor &adam_v, Tensor &target, const OptT &target_h, Tensor &loss,
-                int64_t start, int64_t hidden, int64_t precision, bool sync, double gamma,
-                double alpha, double c1, double c2, double eps, int64_t loss_kind,
-                const OptT &qstats, const OptT &rn_out, const OptT &stamps, const OptT &grad,
-                const OptT &xs, const OptT &xn, double tau, double one_minus_tau) {
+// Per-agent hyperparameters (include/dmdqn.h dmdqn_agent_hparams): lr / gamma_a /
+// tau_a / one_minus_tau_a f32 [NA] tensors on the device of params, or None (the
+// scalar of the same launch); adam_s / adam_d the two Adam factors of the learn
+// as float32.
+dmdqn_agent_hparams make_hparams(const OptT &lr, const OptT &gamma_a, const OptT &tau_a,
+                                 const OptT &one_minus_tau_a, double adam_s, double adam_d,
+                                 int64_t NA, const Tensor &params) {
+    dmdqn_agent_hparams hp{};
+    hp.lr = optr<const float>(lr, at::kFloat, "lr", NA);
+    hp.gamma = optr<const float>(gamma_a, at::kFloat, "gamma_a", NA);
+    hp.tau = optr<const float>(tau_a, at::kFloat, "tau_a", NA);
+    hp.one_minus_tau = optr<const float>(one_minus_tau_a, at::kFloat, "one_minus_tau_a", NA);
+    TORCH_CHECK((hp.tau == nullptr) == (hp.one_minus_tau == nullptr),
+                "tau_a and one_minus_tau_a go together");
+    same_device(params, {opt(lr), opt(gamma_a), opt(tau_a), opt(one_minus_tau_a)},
+                "per-agent hyperparameters must be on the device of params");
+    hp.adam_s = (float)adam_s;
+    hp.adam_d = (float)adam_d;
+    return hp;
+}
+
+// The one learn behind learn_step / learn_step_hp / learn_step_clip.  The kind
+// fixes the C entry points: scalar the plain ones, hp the _hp trio, clip the
+// gradient launch of hp and the clipping Adam launch.  grad: the split learn
+// (gradient launch, then the Adam launch); null: the fused one.  An optional
+// block of a new learn variant belongs here, not in a fourth copy.
+enum class Learn { scalar, hp, clip };
+
+void learn_any(Learn kind, const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
+               const Tensor &ring_d, const Tensor &ring_r, const Tensor &idx, Tensor &params,
+               Tensor &adam_m, Tensor &adam_v, Tensor &target, const OptT &target_h, Tensor &loss,
+               int64_t start, int64_t hidden, int64_t precision, bool sync, double gamma,
+               double alpha, double c1, double c2, double eps, int64_t loss_kind,
+               const OptT &qstats, const OptT &rn_out, const OptT &stamps, const Tensor *grad,
+               const OptT &xs, const OptT &xn, double tau, double one_minus_tau, const OptT &lr,
+               const OptT &gamma_a, const OptT &tau_a, const OptT &one_minus_tau_a, double adam_s,
+               double adam_d, double clip, const OptT &gnorm) {
     const int64_t NA = loss.numel();
     dmdqn_learn_args a = make_learn(ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m,
                                     adam_v, target, target_h, loss, start, hidden, precision, sync,
@@ -424,20 +504,52 @@ void learn_step(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a
     // dqn_agent.py:389-399): float32(tau), float32(1 - tau) from the host; 0 = off
     a.tau = (float)tau;
     a.one_minus_tau = (float)one_minus_tau;
-    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
-    if (grad.has_value()) {  // the split learn: gradient launch, then the Adam launch
-        auto gr = dptr<float>(*grad, at::kFloat, "grad", NA * (int64_t)a.P);
-        check(dmdqn_learn_grad(&a, gr, stream_of(params)), "dmdqn_learn_grad");
-        check(dmdqn_adam_agents(&a, gr, stream_of(params)), "dmdqn_adam_agents");
-        return;
+    dmdqn_agent_hparams hp{};
+    if (kind != Learn::scalar)
+        hp = make_hparams(lr, gamma_a, tau_a, one_minus_tau_a, adam_s, adam_d, NA, params);
+    float *gr = grad ? dptr<float>(*grad, at::kFloat, "grad", NA * (int64_t)a.P) : nullptr;
+    float *gn = nullptr;
+    if (kind == Learn::clip) {
+        same_device(params, {opt(gnorm)}, "gnorm must be on the device of params");
+        gn = optr<float>(gnorm, at::kFloat, "gnorm", NA);
+        // (before the gradient launch: the Adam entry point would refuse it after)
+        TORCH_CHECK((float)clip > 0.0f && (float)clip <= std::numeric_limits<float>::max(),
+                    "clip must be finite and > 0 as float32, got ", clip);
     }
-    check(dmdqn_learn(&a, stream_of(params)), "dmdqn_learn");
+    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
+    void *st = stream_of(params);
+    if (kind == Learn::scalar && gr == nullptr) {
+        check(dmdqn_learn(&a, st), "dmdqn_learn");
+    } else if (kind == Learn::scalar) {
+        check(dmdqn_learn_grad(&a, gr, st), "dmdqn_learn_grad");
+        check(dmdqn_adam_agents(&a, gr, st), "dmdqn_adam_agents");
+    } else if (gr == nullptr) {
+        check(dmdqn_learn_hp(&a, &hp, st), "dmdqn_learn_hp");
+    } else {
+        check(dmdqn_learn_grad_hp(&a, &hp, gr, st), "dmdqn_learn_grad_hp");
+        if (kind == Learn::clip)
+            check(dmdqn_adam_agents_clip(&a, &hp, gr, (float)clip, gn, st),
+                  "dmdqn_adam_agents_clip");
+        else
+            check(dmdqn_adam_agents_hp(&a, &hp, gr, st), "dmdqn_adam_agents_hp");
+    }
 }
 
-// learn_step with per-agent hyperparameters (include/dmdqn.h dmdqn_agent_hparams):
-// lr / gamma_a / tau_a / one_minus_tau_a f32 [NA] device tensors or None (the
-// scalar of the same launch), adam_s / adam_d the two Adam factors of this
-// learn as float32.  All None: exactly learn_step.
+void learn_step(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
+                const Tensor &ring_d, const Tensor &ring_r, const Tensor &idx, Tensor &params,
+                Tensor &adam_m, Tensor &adam_v, Tensor &target, const OptT &target_h, Tensor &loss,
+                int64_t start, int64_t hidden, int64_t precision, bool sync, double gamma,
+                double alpha, double c1, double c2, double eps, int64_t loss_kind,
+                const OptT &qstats, const OptT &rn_out, const OptT &stamps, const OptT &grad,
+                const OptT &xs, const OptT &xn, double tau, double one_minus_tau) {
+    learn_any(Learn::scalar, ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m, adam_v,
+              target, target_h, loss, start, hidden, precision, sync, gamma, alpha, c1, c2, eps,
+              loss_kind, qstats, rn_out, stamps, opt(grad), xs, xn, tau, one_minus_tau,
+              std::nullopt, std::nullopt, std::nullopt, std::nullopt, 1.0, 1.0, 0.0, std::nullopt);
+}
+
+// learn_step with per-agent hyperparameters (make_hparams).  All None: exactly
+// learn_step.
 void learn_step_hp(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a,
                    const Tensor &ring_d, const Tensor &ring_r, const Tensor &idx, Tensor &params,
                    Tensor &adam_m, Tensor &adam_v, Tensor &target, const OptT &target_h,
@@ -447,33 +559,10 @@ void learn_step_hp(const Tensor &ring_s, const Tensor &ring_n, const Tensor &rin
                    const OptT &xs, const OptT &xn, double tau, double one_minus_tau,
                    const OptT &lr, const OptT &gamma_a, const OptT &tau_a,
                    const OptT &one_minus_tau_a, double adam_s, double adam_d) {
-    const int64_t NA = loss.numel();
-    dmdqn_learn_args a = make_learn(ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m,
-                                    adam_v, target, target_h, loss, start, hidden, precision, sync,
-                                    gamma, alpha, c1, c2, eps, loss_kind, qstats, rn_out,
-                                    std::nullopt, stamps, NA, NA, xs, xn);
-    a.tau = (float)tau;
-    a.one_minus_tau = (float)one_minus_tau;
-    dmdqn_agent_hparams hp{};
-    hp.lr = optr<const float>(lr, at::kFloat, "lr", NA);
-    hp.gamma = optr<const float>(gamma_a, at::kFloat, "gamma_a", NA);
-    hp.tau = optr<const float>(tau_a, at::kFloat, "tau_a", NA);
-    hp.one_minus_tau = optr<const float>(one_minus_tau_a, at::kFloat, "one_minus_tau_a", NA);
-    TORCH_CHECK((hp.tau == nullptr) == (hp.one_minus_tau == nullptr),
-                "tau_a and one_minus_tau_a go together");
-    for (const OptT *t : {&lr, &gamma_a, &tau_a, &one_minus_tau_a})
-        TORCH_CHECK(!t->has_value() || (*t)->device() == params.device(),
-                    "per-agent hyperparameters must be on the device of params");
-    hp.adam_s = (float)adam_s;
-    hp.adam_d = (float)adam_d;
-    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
-    if (grad.has_value()) {  // the split learn: gradient launch, then the Adam launch
-        auto gr = dptr<float>(*grad, at::kFloat, "grad", NA * (int64_t)a.P);
-        check(dmdqn_learn_grad_hp(&a, &hp, gr, stream_of(params)), "dmdqn_learn_grad_hp");
-        check(dmdqn_adam_agents_hp(&a, &hp, gr, stream_of(params)), "dmdqn_adam_agents_hp");
-        return;
-    }
-    check(dmdqn_learn_hp(&a, &hp, stream_of(params)), "dmdqn_learn_hp");
+    learn_any(Learn::hp, ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m, adam_v,
+              target, target_h, loss, start, hidden, precision, sync, gamma, alpha, c1, c2, eps,
+              loss_kind, qstats, rn_out, stamps, opt(grad), xs, xn, tau, one_minus_tau, lr,
+              gamma_a, tau_a, one_minus_tau_a, adam_s, adam_d, 0.0, std::nullopt);
 }
 
 // learn_step_hp as the split learn (grad required) with the gradient of every
@@ -490,34 +579,10 @@ void learn_step_clip(const Tensor &ring_s, const Tensor &ring_n, const Tensor &r
                      double one_minus_tau, const OptT &lr, const OptT &gamma_a, const OptT &tau_a,
                      const OptT &one_minus_tau_a, double adam_s, double adam_d, double clip,
                      const OptT &gnorm) {
-    const int64_t NA = loss.numel();
-    dmdqn_learn_args a = make_learn(ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m,
-                                    adam_v, target, target_h, loss, start, hidden, precision, sync,
-                                    gamma, alpha, c1, c2, eps, loss_kind, qstats, rn_out,
-                                    std::nullopt, stamps, NA, NA, xs, xn);
-    a.tau = (float)tau;
-    a.one_minus_tau = (float)one_minus_tau;
-    dmdqn_agent_hparams hp{};
-    hp.lr = optr<const float>(lr, at::kFloat, "lr", NA);
-    hp.gamma = optr<const float>(gamma_a, at::kFloat, "gamma_a", NA);
-    hp.tau = optr<const float>(tau_a, at::kFloat, "tau_a", NA);
-    hp.one_minus_tau = optr<const float>(one_minus_tau_a, at::kFloat, "one_minus_tau_a", NA);
-    TORCH_CHECK((hp.tau == nullptr) == (hp.one_minus_tau == nullptr),
-                "tau_a and one_minus_tau_a go together");
-    for (const OptT *t : {&lr, &gamma_a, &tau_a, &one_minus_tau_a, &gnorm})
-        TORCH_CHECK(!t->has_value() || (*t)->device() == params.device(),
-                    "per-agent hyperparameters and gnorm must be on the device of params");
-    hp.adam_s = (float)adam_s;
-    hp.adam_d = (float)adam_d;
-    auto gr = dptr<float>(grad, at::kFloat, "grad", NA * (int64_t)a.P);
-    auto gn = optr<float>(gnorm, at::kFloat, "gnorm", NA);
-    // (before the gradient launch: the Adam entry point would refuse it after)
-    TORCH_CHECK((float)clip > 0.0f && (float)clip <= std::numeric_limits<float>::max(),
-                "clip must be finite and > 0 as float32, got ", clip);
-    c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
-    check(dmdqn_learn_grad_hp(&a, &hp, gr, stream_of(params)), "dmdqn_learn_grad_hp");
-    check(dmdqn_adam_agents_clip(&a, &hp, gr, (float)clip, gn, stream_of(params)),
-          "dmdqn_adam_agents_clip");
+    learn_any(Learn::clip, ring_s, ring_n, ring_a, ring_d, ring_r, idx, params, adam_m, adam_v,
+              target, target_h, loss, start, hidden, precision, sync, gamma, alpha, c1, c2, eps,
+              loss_kind, qstats, rn_out, stamps, &grad, xs, xn, tau, one_minus_tau, lr, gamma_a,
+              tau_a, one_minus_tau_a, adam_s, adam_d, clip, gnorm);
 }
 
 // Two consecutive learns of every agent in one launch (dmdqn_learn_pair): the
@@ -550,17 +615,8 @@ void learn_pair(const Tensor &ring_s, const Tensor &ring_n, const Tensor &ring_a
                           i ? rn_out1 : rn_out0, std::nullopt, std::nullopt, NA, NA);
         a[i].tau = (float)tau;
         a[i].one_minus_tau = (float)one_minus_tau;
-        hp[i] = dmdqn_agent_hparams{};
-        hp[i].lr = optr<const float>(lr, at::kFloat, "lr", NA);
-        hp[i].gamma = optr<const float>(gamma_a, at::kFloat, "gamma_a", NA);
-        hp[i].tau = optr<const float>(tau_a, at::kFloat, "tau_a", NA);
-        hp[i].one_minus_tau = optr<const float>(one_minus_tau_a, at::kFloat, "one_minus_tau_a", NA);
-        hp[i].adam_s = (float)fa[0];
-        hp[i].adam_d = (float)fa[1];
+        hp[i] = make_hparams(lr, gamma_a, tau_a, one_minus_tau_a, fa[0], fa[1], NA, params);
     }
-    for (const OptT *t : {&lr, &gamma_a, &tau_a, &one_minus_tau_a})
-        TORCH_CHECK(!t->has_value() || (*t)->device() == params.device(),
-                    "per-agent hyperparameters must be on the device of params");
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
     check(dmdqn_learn_pair(&a[0], &a[1], &hp[0], &hp[1], stream_of(params)), "dmdqn_learn_pair");
 }
@@ -588,20 +644,37 @@ void learn_shared_grad(const Tensor &ring_s, const Tensor &ring_n, const Tensor 
           "dmdqn_learn_shared_grad");
 }
 
+// The shared net as the flat Adam step sees it: n weights, their Adam slots,
+// target and gradient, and the f16 shadows k_adam writes (the shared net is
+// fp16-only).
+struct FlatNet {
+    int64_t n;
+    float *w, *m, *v, *t, *g;
+    uint16_t *th, *wh;
+};
+
+FlatNet flat_net(Tensor &params, Tensor &adam_m, Tensor &adam_v, Tensor &target,
+                 const OptT &target_h, const OptT &params_h, const Tensor &grad) {
+    FlatNet f{};
+    f.n = params.numel();
+    f.w = dptr<float>(params, at::kFloat, "params");
+    f.m = dptr<float>(adam_m, at::kFloat, "adam_m", f.n);
+    f.v = dptr<float>(adam_v, at::kFloat, "adam_v", f.n);
+    f.t = dptr<float>(target, at::kFloat, "target", f.n);
+    f.g = dptr<float>(grad, at::kFloat, "grad", f.n);
+    f.th = h16ptr(target_h, "target_h", 1, f.n);
+    f.wh = h16ptr(params_h, "params_h", 1, f.n);
+    return f;
+}
+
 void adam(Tensor &params, Tensor &adam_m, Tensor &adam_v, Tensor &target, const OptT &target_h,
           const OptT &params_h, const Tensor &grad, double gscale, double alpha, double c1,
           double c2, double eps, bool sync) {
-    const int64_t n = params.numel();
-    auto w = dptr<float>(params, at::kFloat, "params");
-    auto m = dptr<float>(adam_m, at::kFloat, "adam_m", n);
-    auto v = dptr<float>(adam_v, at::kFloat, "adam_v", n);
-    auto t = dptr<float>(target, at::kFloat, "target", n);
-    auto gr = dptr<float>(grad, at::kFloat, "grad", n);
+    const FlatNet f = flat_net(params, adam_m, adam_v, target, target_h, params_h, grad);
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
-    // k_adam writes f16 shadows (the shared net is fp16-only)
-    check(dmdqn_adam(w, m, v, t, h16ptr(target_h, "target_h", 1, n), h16ptr(params_h, "params_h", 1, n), gr,
-                     int32_of(n, "n"), (float)gscale, (float)alpha, (float)c1, (float)c2,
-                     (float)eps, sync ? 1 : 0, stream_of(params)),
+    check(dmdqn_adam(f.w, f.m, f.v, f.t, f.th, f.wh, f.g, int32_of(f.n, "n"), (float)gscale,
+                     (float)alpha, (float)c1, (float)c2, (float)eps, sync ? 1 : 0,
+                     stream_of(params)),
           "dmdqn_adam");
 }
 
@@ -609,69 +682,70 @@ void adam_slabs(Tensor &params, Tensor &adam_m, Tensor &adam_v, Tensor &target,
                 const OptT &target_h, const OptT &params_h, const Tensor &slab, Tensor &grad,
                 double scale, double gscale, double alpha, double c1, double c2, double eps,
                 bool sync) {
-    const int64_t n = params.numel();
-    auto w = dptr<float>(params, at::kFloat, "params");
-    auto m = dptr<float>(adam_m, at::kFloat, "adam_m", n);
-    auto v = dptr<float>(adam_v, at::kFloat, "adam_v", n);
-    auto t = dptr<float>(target, at::kFloat, "target", n);
-    auto gr = dptr<float>(grad, at::kFloat, "grad", n);
-    TORCH_CHECK(slab.numel() % n == 0, "slab must be [n_slabs, P]");
+    const FlatNet f = flat_net(params, adam_m, adam_v, target, target_h, params_h, grad);
+    TORCH_CHECK(slab.numel() % f.n == 0, "slab must be [n_slabs, P]");
     auto sl = dptr<float>(slab, at::kFloat, "slab");
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
-    check(dmdqn_adam_slabs(w, m, v, t, h16ptr(target_h, "target_h", 1, n),
-                           h16ptr(params_h, "params_h", 1, n), sl, int32_of(slab.numel() / n, "n_slabs"),
-                           gr, (float)scale, int32_of(n, "n"), (float)gscale, (float)alpha,
-                           (float)c1, (float)c2, (float)eps, sync ? 1 : 0, stream_of(params)),
+    check(dmdqn_adam_slabs(f.w, f.m, f.v, f.t, f.th, f.wh, sl,
+                           int32_of(slab.numel() / f.n, "n_slabs"), f.g, (float)scale,
+                           int32_of(f.n, "n"), (float)gscale, (float)alpha, (float)c1, (float)c2,
+                           (float)eps, sync ? 1 : 0, stream_of(params)),
           "dmdqn_adam_slabs");
 }
 
+// Ph, the row stride of an optional 16-bit shadow [rows, Ph] beside f32 rows of
+// P values (P without one).
+int64_t shadow_stride(const OptT &target_h, int64_t rows, int64_t P, const char *msg) {
+    const int64_t Ph = target_h.has_value() ? target_h->numel() / rows : P;
+    TORCH_CHECK(!target_h.has_value() || (target_h->numel() % rows == 0 && Ph >= P), msg);
+    return Ph;
+}
+
+// NW online nets [NW, P], their f32 targets and the targets' optional shadow.
+struct Nets {
+    int64_t NW, P, Ph;
+    float *params, *target;
+};
+
+Nets nets_of(const Tensor &params, Tensor &target, const OptT &target_h) {
+    Nets n{};
+    std::tie(n.NW, n.P) = dims2(params, "params must be [NW, P]");
+    n.params = dptr<float>(params, at::kFloat, "params");
+    n.target = dptr<float>(target, at::kFloat, "target", n.NW * n.P);
+    n.Ph = shadow_stride(target_h, n.NW, n.P, "target_h must be [NW, Ph] with Ph >= P");
+    return n;
+}
+
 void target_sync(const Tensor &params, Tensor &target, const OptT &target_h, int64_t precision) {
-    TORCH_CHECK(params.dim() == 2, "params must be [NW, P]");
-    const int64_t NW = params.size(0), P = params.size(1);
-    auto p = dptr<float>(params, at::kFloat, "params");
-    auto t = dptr<float>(target, at::kFloat, "target", NW * P);
-    const int64_t Ph = target_h.has_value() ? target_h->numel() / NW : P;
-    TORCH_CHECK(!target_h.has_value() || (target_h->numel() % NW == 0 && Ph >= P),
-                "target_h must be [NW, Ph] with Ph >= P");
+    const Nets n = nets_of(params, target, target_h);
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
-    check(dmdqn_target_sync(p, t, h16ptr(target_h, "target_h", precision), (int)NW, (int)P, (int)Ph,
-                            (int)precision, stream_of(params)),
+    check(dmdqn_target_sync(n.params, n.target, h16ptr(target_h, "target_h", precision), (int)n.NW,
+                            (int)n.P, (int)n.Ph, (int)precision, stream_of(params)),
           "dmdqn_target_sync");
 }
 
 void target_soft_update(const Tensor &params, Tensor &target, const OptT &target_h,
                         int64_t precision, double tau, double one_minus_tau) {
-    TORCH_CHECK(params.dim() == 2, "params must be [NW, P]");
-    const int64_t NW = params.size(0), P = params.size(1);
-    auto p = dptr<float>(params, at::kFloat, "params");
-    auto t = dptr<float>(target, at::kFloat, "target", NW * P);
-    const int64_t Ph = target_h.has_value() ? target_h->numel() / NW : P;
-    TORCH_CHECK(!target_h.has_value() || (target_h->numel() % NW == 0 && Ph >= P),
-                "target_h must be [NW, Ph] with Ph >= P");
+    const Nets n = nets_of(params, target, target_h);
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
-    check(dmdqn_target_soft_update(p, t, h16ptr(target_h, "target_h", precision), (int)NW, (int)P,
-                                   (int)Ph, (int)precision, (float)tau, (float)one_minus_tau,
-                                   stream_of(params)),
+    check(dmdqn_target_soft_update(n.params, n.target, h16ptr(target_h, "target_h", precision),
+                                   (int)n.NW, (int)n.P, (int)n.Ph, (int)precision, (float)tau,
+                                   (float)one_minus_tau, stream_of(params)),
           "dmdqn_target_soft_update");
 }
 
 // target_soft_update with one tau per net: tau / one_minus_tau f32 [NW].
 void target_soft_update_hp(const Tensor &params, Tensor &target, const OptT &target_h,
                            int64_t precision, const Tensor &tau, const Tensor &one_minus_tau) {
-    TORCH_CHECK(params.dim() == 2, "params must be [NW, P]");
-    const int64_t NW = params.size(0), P = params.size(1);
-    auto p = dptr<float>(params, at::kFloat, "params");
-    auto t = dptr<float>(target, at::kFloat, "target", NW * P);
-    const int64_t Ph = target_h.has_value() ? target_h->numel() / NW : P;
-    TORCH_CHECK(!target_h.has_value() || (target_h->numel() % NW == 0 && Ph >= P),
-                "target_h must be [NW, Ph] with Ph >= P");
-    auto ta = dptr<const float>(tau, at::kFloat, "tau", NW);
-    auto oa = dptr<const float>(one_minus_tau, at::kFloat, "one_minus_tau", NW);
-    TORCH_CHECK(tau.device() == params.device() && one_minus_tau.device() == params.device(),
+    const Nets n = nets_of(params, target, target_h);
+    auto ta = dptr<const float>(tau, at::kFloat, "tau", n.NW);
+    auto oa = dptr<const float>(one_minus_tau, at::kFloat, "one_minus_tau", n.NW);
+    same_device(params, {&tau, &one_minus_tau},
                 "tau / one_minus_tau must be on the device of params");
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
-    check(dmdqn_target_soft_update_hp(p, t, h16ptr(target_h, "target_h", precision), (int)NW,
-                                      (int)P, (int)Ph, (int)precision, ta, oa, stream_of(params)),
+    check(dmdqn_target_soft_update_hp(n.params, n.target, h16ptr(target_h, "target_h", precision),
+                                      (int)n.NW, (int)n.P, (int)n.Ph, (int)precision, ta, oa,
+                                      stream_of(params)),
           "dmdqn_target_soft_update_hp");
 }
 
@@ -693,11 +767,10 @@ void q_argmax(const Tensor &params, int64_t hidden, int64_t precision, const Ten
 
 // ---------------------------------------------------------------- population-based training
 void pbt_score(const Tensor &reward, Tensor &fitness) {
-    TORCH_CHECK(reward.dim() == 2, "reward must be [E, A]");
-    const int64_t E = reward.size(0), A = reward.size(1);
+    const auto [E, A] = dims2(reward, "reward must be [E, A]");
     auto r = dptr<const double>(reward, at::kDouble, "reward");
     auto f = dptr<double>(fitness, at::kDouble, "fitness", E);
-    TORCH_CHECK(fitness.device() == reward.device(), "fitness must be on the device of reward");
+    same_device(reward, {&fitness}, "fitness must be on the device of reward");
     c10::hip::HIPGuardMasqueradingAsCUDA g(reward.device());
     check(dmdqn_pbt_score(r, int32_of(E, "E"), int32_of(A, "A"), f, stream_of(reward)),
           "dmdqn_pbt_score");
@@ -708,8 +781,7 @@ void pbt_select(const Tensor &fitness, int64_t n, Tensor &rank, Tensor &src) {
     auto f = dptr<const double>(fitness, at::kDouble, "fitness");
     auto r = dptr<int32_t>(rank, at::kInt, "rank", E);
     auto s = dptr<int32_t>(src, at::kInt, "src", E);
-    TORCH_CHECK(rank.device() == fitness.device() && src.device() == fitness.device(),
-                "rank / src must be on the device of fitness");
+    same_device(fitness, {&rank, &src}, "rank / src must be on the device of fitness");
     c10::hip::HIPGuardMasqueradingAsCUDA g(fitness.device());
     check(dmdqn_pbt_select(f, int32_of(E, "E"), int32_of(n, "n"), r, s, stream_of(fitness)),
           "dmdqn_pbt_select");
@@ -717,22 +789,18 @@ void pbt_select(const Tensor &fitness, int64_t n, Tensor &rank, Tensor &src) {
 
 void pbt_exchange(const Tensor &src, int64_t A, Tensor &params, Tensor &target, Tensor &adam_m,
                   Tensor &adam_v, const OptT &target_h) {
-    TORCH_CHECK(params.dim() == 2, "params must be [E * A, P]");
-    const int64_t E = src.numel(), NA = params.size(0), P = params.size(1);
+    const auto [NA, P] = dims2(params, "params must be [E * A, P]");
+    const int64_t E = src.numel();
     TORCH_CHECK(A >= 1 && NA == E * A, "params holds ", NA, " rows, src ", E, " replicas of ", A);
     auto sp = dptr<const int32_t>(src, at::kInt, "src");
     auto p = dptr<float>(params, at::kFloat, "params");
     auto t = dptr<float>(target, at::kFloat, "target", NA * P);
     auto m = dptr<float>(adam_m, at::kFloat, "adam_m", NA * P);
     auto v = dptr<float>(adam_v, at::kFloat, "adam_v", NA * P);
-    const int64_t Ph = target_h.has_value() ? target_h->numel() / NA : P;
-    TORCH_CHECK(!target_h.has_value() || (target_h->numel() % NA == 0 && Ph >= P),
-                "target_h must be [E * A, Ph] with Ph >= P");
-    TORCH_CHECK(target.device() == params.device() && adam_m.device() == params.device() &&
-                    adam_v.device() == params.device() && src.device() == params.device(),
+    const int64_t Ph = shadow_stride(target_h, NA, P, "target_h must be [E * A, Ph] with Ph >= P");
+    same_device(params, {&target, &adam_m, &adam_v, &src},
                 "every tensor must be on the device of params");
-    TORCH_CHECK(!target_h.has_value() || target_h->device() == params.device(),
-                "target_h must be on the device of params");
+    same_device(params, {opt(target_h)}, "target_h must be on the device of params");
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
     check(dmdqn_pbt_exchange(sp, int32_of(E, "E"), int32_of(A, "A"), int32_of(P, "P"),
                              int32_of(Ph, "Ph"), p, t, m, v, h16ptr(target_h, "target_h"),
@@ -747,8 +815,7 @@ void pbt_exchange(const Tensor &src, int64_t A, Tensor &params, Tensor &target, 
 void net_probe(const Tensor &ring_s, const Tensor &idx, const Tensor &params, int64_t start,
                int64_t hidden, int64_t precision, Tensor &counts, Tensor &stats,
                const OptT &dead_mask) {
-    TORCH_CHECK(params.dim() == 2, "params must be [NA, P]");
-    const int64_t NA = params.size(0), P = params.size(1);
+    const auto [NA, P] = dims2(params, "params must be [NA, P]");
     TORCH_CHECK(NA > 0 && idx.numel() % NA == 0, "idx must be [NA, batch]");
     const int64_t B = idx.numel() / NA;
     TORCH_CHECK(ring_s.numel() % (NA * DMDQN_ROW_BYTES) == 0 && ring_s.numel() > 0,
@@ -764,11 +831,9 @@ void net_probe(const Tensor &ring_s, const Tensor &idx, const Tensor &params, in
     a.counts = dptr<int32_t>(counts, at::kInt, "counts", NA * DMDQN_PROBE_COUNTS);
     a.stats = dptr<double>(stats, at::kDouble, "stats", NA * DMDQN_PROBE_STATS);
     a.dead_mask = optr<uint32_t>(dead_mask, at::kInt, "dead_mask", NA * 2 * 4);
-    TORCH_CHECK(ring_s.device() == params.device() && idx.device() == params.device() &&
-                    counts.device() == params.device() && stats.device() == params.device(),
+    same_device(params, {&ring_s, &idx, &counts, &stats},
                 "every tensor must be on the device of params");
-    TORCH_CHECK(!dead_mask.has_value() || dead_mask->device() == params.device(),
-                "dead_mask must be on the device of params");
+    same_device(params, {opt(dead_mask)}, "dead_mask must be on the device of params");
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
     check(dmdqn_net_probe(&a, stream_of(params)), "dmdqn_net_probe");
 }
@@ -777,13 +842,11 @@ void net_probe(const Tensor &ring_s, const Tensor &idx, const Tensor &params, in
 // mode 0 of x, mode 1 of x / (sqrt(y) + eps); out f64 [NW, 6] in Keras order.
 void layer_norms(const Tensor &x, const OptT &y, double eps, int64_t mode, int64_t hidden,
                  Tensor &out) {
-    TORCH_CHECK(x.dim() == 2, "x must be [NW, P]");
-    const int64_t NW = x.size(0), P = x.size(1);
+    const auto [NW, P] = dims2(x, "x must be [NW, P]");
     auto xp = dptr<const float>(x, at::kFloat, "x");
     auto yp = optr<const float>(y, at::kFloat, "y", NW * P);
     auto o = dptr<double>(out, at::kDouble, "out", NW * 6);
-    TORCH_CHECK(out.device() == x.device() && (!y.has_value() || y->device() == x.device()),
-                "every tensor must be on the device of x");
+    same_device(x, {&out, opt(y)}, "every tensor must be on the device of x");
     c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
     check(dmdqn_layer_norms(xp, yp, (float)eps, int32_of(mode, "mode"), int32_of(NW, "NW"),
                             int32_of(P, "P"), int32_of(hidden, "hidden"), o, stream_of(x)),
@@ -797,8 +860,7 @@ void layer_norms(const Tensor &x, const OptT &y, double eps, int64_t mode, int64
 void redo(const Tensor &dead_mask, Tensor &streak, Tensor &params, Tensor &adam_m, Tensor &adam_v,
           int64_t hidden, int64_t agent0, int64_t seed, int64_t round, int64_t patience,
           double lim1, double lim2, Tensor &recycled, Tensor &n_recycled) {
-    TORCH_CHECK(params.dim() == 2, "params must be [NA, P]");
-    const int64_t NA = params.size(0), P = params.size(1);
+    const auto [NA, P] = dims2(params, "params must be [NA, P]");
     TORCH_CHECK(NA > 0, "params must be [NA, P] with NA > 0");
     TORCH_CHECK(round >= 0 && round <= (int64_t)UINT32_MAX, "round out of uint32 range");
     dmdqn_redo_args a{};
@@ -813,9 +875,7 @@ void redo(const Tensor &dead_mask, Tensor &streak, Tensor &params, Tensor &adam_
     a.adam_v = dptr<float>(adam_v, at::kFloat, "adam_v", NA * P);
     a.recycled = dptr<uint32_t>(recycled, at::kInt, "recycled", NA * 2 * 4);
     a.n_recycled = dptr<int32_t>(n_recycled, at::kInt, "n_recycled", NA * 2);
-    TORCH_CHECK(dead_mask.device() == params.device() && streak.device() == params.device() &&
-                    adam_m.device() == params.device() && adam_v.device() == params.device() &&
-                    recycled.device() == params.device() && n_recycled.device() == params.device(),
+    same_device(params, {&dead_mask, &streak, &adam_m, &adam_v, &recycled, &n_recycled},
                 "every tensor must be on the device of params");
     c10::hip::HIPGuardMasqueradingAsCUDA g(params.device());
     check(dmdqn_redo(&a, stream_of(params)), "dmdqn_redo");
@@ -835,91 +895,12 @@ void act_rule(const Tensor &obs, int64_t R, int64_t C, int64_t rule, Tensor &act
     auto o = dptr<const float>(obs, at::kFloat, "obs");
     auto a = dptr<int32_t>(actions, at::kInt, "actions", E * A);
     auto sc = optr<int32_t>(score, at::kInt, "score", E * A * 4);
-    TORCH_CHECK(actions.device() == obs.device() &&
-                    (!score.has_value() || score->device() == obs.device()),
-                "every tensor must be on the device of obs");
+    same_device(obs, {&actions, opt(score)}, "every tensor must be on the device of obs");
     c10::hip::HIPGuardMasqueradingAsCUDA g(obs.device());
     check(dmdqn_act_rule(int32_of(R, "R"), int32_of(C, "C"), int32_of(E, "E"),
                          int32_of(rule, "rule"), o, a, sc, stream_of(obs)),
           "dmdqn_act_rule");
 }
-
-// Meta kernels: the ops only mutate their (a!) arguments, so tracing needs no
-// shape function beyond "nothing is returned".
-void pbt_score_meta(const Tensor &, Tensor &) {}
-void net_probe_meta(const Tensor &, const Tensor &, const Tensor &, int64_t, int64_t, int64_t,
-                    Tensor &, Tensor &, const OptT &) {}
-void layer_norms_meta(const Tensor &, const OptT &, double, int64_t, int64_t, Tensor &) {}
-void redo_meta(const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, int64_t, int64_t, int64_t,
-               int64_t, int64_t, double, double, Tensor &, Tensor &) {}
-void act_rule_meta(const Tensor &, int64_t, int64_t, int64_t, Tensor &, const OptT &) {}
-void pbt_select_meta(const Tensor &, int64_t, Tensor &, Tensor &) {}
-void pbt_exchange_meta(const Tensor &, int64_t, Tensor &, Tensor &, Tensor &, Tensor &,
-                       const OptT &) {}
-void mt_seed_meta(Tensor &, const Tensor &, const std::string &) {}
-void mt_draw_u32_meta(Tensor &, int64_t, Tensor &) {}
-void act_meta(Tensor &, int64_t, double, int64_t, const OptT &, Tensor &, bool) {}
-void observe_meta(int64_t, int64_t, const Tensor &, const Tensor &, const Tensor &, int64_t,
-                  const OptT &, const OptT &, const OptT &, const OptT &) {}
-void replay_store_meta(int64_t, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                       const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, Tensor &) {}
-void replay_sample_meta(Tensor &, int64_t, int64_t, int64_t, Tensor &, int64_t) {}
-void replay_nstep_commit_meta(int64_t, int64_t, const Tensor &, const Tensor &, const Tensor &,
-                              const Tensor &, const Tensor &, Tensor &, Tensor &, Tensor &,
-                              Tensor &, Tensor &, double, const OptT &) {}
-void replay_store_f32_meta(int64_t, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                           const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, Tensor &) {}
-void replay_gather_f32_meta(const Tensor &, const Tensor &, const Tensor &, int64_t, Tensor &,
-                            Tensor &) {}
-void sim_reset_meta(at::TensorList, at::TensorList, at::IntArrayRef, const OptT &) {}
-void sim_step_meta(at::TensorList, at::TensorList, at::IntArrayRef, at::ArrayRef<double>,
-                   const OptT &, int64_t, int64_t, int64_t, int64_t, Tensor &, Tensor &, Tensor &,
-                   Tensor &) {}
-void env_step_meta(at::TensorList, at::TensorList, at::IntArrayRef, at::ArrayRef<double>, int64_t,
-                   int64_t, int64_t, int64_t, Tensor &, Tensor &, Tensor &, Tensor &, Tensor &,
-                   const OptT &, Tensor &, double, int64_t, int64_t, Tensor &, Tensor &,
-                   const Tensor &, Tensor &, const Tensor &, int64_t, Tensor &, Tensor &, Tensor &,
-                   Tensor &, Tensor &, Tensor &) {}
-void learn_step_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                     const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, const OptT &, Tensor &,
-                     int64_t, int64_t, int64_t, bool, double, double, double, double, double,
-                     int64_t, const OptT &, const OptT &, const OptT &, const OptT &, const OptT &,
-                     const OptT &, double, double) {}
-void learn_step_hp_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                        const Tensor &, const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &,
-                        const OptT &, Tensor &, int64_t, int64_t, int64_t, bool, double, double,
-                        double, double, double, int64_t, const OptT &, const OptT &, const OptT &,
-                        const OptT &, const OptT &, const OptT &, double, double, const OptT &,
-                        const OptT &, const OptT &, const OptT &, double, double) {}
-void learn_step_clip_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                          const Tensor &, const Tensor &, Tensor &, Tensor &, Tensor &, Tensor &,
-                          const OptT &, Tensor &, int64_t, int64_t, int64_t, bool, double, double,
-                          double, double, double, int64_t, const OptT &, const OptT &, const OptT &,
-                          Tensor &, const OptT &, const OptT &, double, double, const OptT &,
-                          const OptT &, const OptT &, const OptT &, double, double, double,
-                          const OptT &) {}
-void learn_pair_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                     Tensor &, Tensor &, Tensor &, Tensor &, Tensor &, const Tensor &,
-                     const Tensor &, Tensor &, Tensor &, int64_t, int64_t, int64_t, int64_t, double,
-                     at::ArrayRef<double>, at::ArrayRef<double>, int64_t, const OptT &,
-                     const OptT &, const OptT &, const OptT &, double, double, const OptT &,
-                     const OptT &, const OptT &, const OptT &, at::ArrayRef<double>,
-                     at::ArrayRef<double>) {}
-void learn_shared_grad_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                            const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                            const Tensor &, const Tensor &, Tensor &, int64_t, double, int64_t,
-                            const OptT &, const OptT &, Tensor &, const OptT &, double,
-                            const OptT &) {}
-void adam_slabs_meta(Tensor &, Tensor &, Tensor &, Tensor &, const OptT &, const OptT &,
-                     const Tensor &, Tensor &, double, double, double, double, double, double,
-                     bool) {}
-void adam_meta(Tensor &, Tensor &, Tensor &, Tensor &, const OptT &, const OptT &, const Tensor &,
-               double, double, double, double, double, bool) {}
-void target_sync_meta(const Tensor &, Tensor &, const OptT &, int64_t) {}
-void target_soft_update_meta(const Tensor &, Tensor &, const OptT &, int64_t, double, double) {}
-void target_soft_update_hp_meta(const Tensor &, Tensor &, const OptT &, int64_t, const Tensor &,
-                                const Tensor &) {}
-void q_argmax_meta(const Tensor &, int64_t, int64_t, const Tensor &, Tensor &, const OptT &, bool) {}
 
 }  // namespace
 
@@ -1056,68 +1037,32 @@ TORCH_LIBRARY(dmdqn, m) {
           "Tensor(b!)? score) -> ()");
 }
 
+// Every operator, once: both dispatch keys below are filled from this list, so
+// an operator cannot have one kernel and not the other.
+#define DMDQN_OPS(X)                                                                              \
+    X(mt_seed) X(mt_draw_u32) X(act) X(observe) X(replay_store) X(replay_sample)                  \
+    X(replay_store_f32) X(replay_gather_f32) X(replay_nstep_commit) X(sim_reset) X(sim_step)      \
+    X(env_step) X(learn_step) X(learn_step_hp) X(learn_step_clip) X(learn_pair)                   \
+    X(learn_shared_grad) X(adam) X(adam_slabs) X(target_sync) X(target_soft_update)               \
+    X(target_soft_update_hp) X(q_argmax) X(pbt_score) X(pbt_select) X(pbt_exchange) X(net_probe)  \
+    X(layer_norms) X(redo) X(act_rule)
+
 TORCH_LIBRARY_IMPL(dmdqn, CUDA, m) {
-    m.impl("mt_seed", &mt_seed);
-    m.impl("mt_draw_u32", &mt_draw_u32);
-    m.impl("act", &act);
-    m.impl("observe", &observe);
-    m.impl("replay_store", &replay_store);
-    m.impl("replay_sample", &replay_sample);
-    m.impl("replay_store_f32", &replay_store_f32);
-    m.impl("replay_gather_f32", &replay_gather_f32);
-    m.impl("replay_nstep_commit", &replay_nstep_commit);
-    m.impl("sim_reset", &sim_reset);
-    m.impl("sim_step", &sim_step);
-    m.impl("env_step", &env_step);
-    m.impl("learn_step", &learn_step);
-    m.impl("learn_step_hp", &learn_step_hp);
-    m.impl("learn_step_clip", &learn_step_clip);
-    m.impl("learn_pair", &learn_pair);
-    m.impl("learn_shared_grad", &learn_shared_grad);
-    m.impl("adam", &adam);
-    m.impl("adam_slabs", &adam_slabs);
-    m.impl("target_sync", &target_sync);
-    m.impl("target_soft_update", &target_soft_update);
-    m.impl("target_soft_update_hp", &target_soft_update_hp);
-    m.impl("q_argmax", &q_argmax);
-    m.impl("pbt_score", &pbt_score);
-    m.impl("pbt_select", &pbt_select);
-    m.impl("pbt_exchange", &pbt_exchange);
-    m.impl("net_probe", &net_probe);
-    m.impl("layer_norms", &layer_norms);
-    m.impl("redo", &redo);
-    m.impl("act_rule", &act_rule);
+#define X(op) m.impl(#op, &op);
+    DMDQN_OPS(X)
+#undef X
 }
 
+// Meta kernels: the ops only mutate their (a!) arguments, so tracing needs no
+// shape function beyond "nothing is returned" -- the implementation's own
+// signature with an empty body.
+template <typename F> struct NoLaunch;
+template <typename... A> struct NoLaunch<void(A...)> {
+    static void run(A...) {}
+};
+
 TORCH_LIBRARY_IMPL(dmdqn, Meta, m) {
-    m.impl("mt_seed", &mt_seed_meta);
-    m.impl("mt_draw_u32", &mt_draw_u32_meta);
-    m.impl("act", &act_meta);
-    m.impl("observe", &observe_meta);
-    m.impl("replay_store", &replay_store_meta);
-    m.impl("replay_sample", &replay_sample_meta);
-    m.impl("replay_store_f32", &replay_store_f32_meta);
-    m.impl("replay_gather_f32", &replay_gather_f32_meta);
-    m.impl("replay_nstep_commit", &replay_nstep_commit_meta);
-    m.impl("sim_reset", &sim_reset_meta);
-    m.impl("sim_step", &sim_step_meta);
-    m.impl("env_step", &env_step_meta);
-    m.impl("learn_step", &learn_step_meta);
-    m.impl("learn_step_hp", &learn_step_hp_meta);
-    m.impl("learn_step_clip", &learn_step_clip_meta);
-    m.impl("learn_pair", &learn_pair_meta);
-    m.impl("learn_shared_grad", &learn_shared_grad_meta);
-    m.impl("adam", &adam_meta);
-    m.impl("adam_slabs", &adam_slabs_meta);
-    m.impl("target_sync", &target_sync_meta);
-    m.impl("target_soft_update", &target_soft_update_meta);
-    m.impl("target_soft_update_hp", &target_soft_update_hp_meta);
-    m.impl("q_argmax", &q_argmax_meta);
-    m.impl("pbt_score", &pbt_score_meta);
-    m.impl("pbt_select", &pbt_select_meta);
-    m.impl("pbt_exchange", &pbt_exchange_meta);
-    m.impl("net_probe", &net_probe_meta);
-    m.impl("layer_norms", &layer_norms_meta);
-    m.impl("redo", &redo_meta);
-    m.impl("act_rule", &act_rule_meta);
+#define X(op) m.impl(#op, &NoLaunch<decltype(op)>::run);
+    DMDQN_OPS(X)
+#undef X
 }

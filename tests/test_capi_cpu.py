@@ -69,6 +69,19 @@ def test_torch_ops_registered_without_gpu(lib):
         D.mt_seed(torch.zeros((1, 625), dtype=torch.int32), torch.zeros(1, dtype=torch.int64), "np")
 
 
+def test_every_operator_has_a_device_and_a_meta_kernel_and_no_cpu_kernel(lib):
+    """Both impl blocks of dmdqn_torch.cpp come from one list of operators:
+    every operator has a CUDA (HIP) kernel and a Meta kernel, none a CPU one."""
+    import torch
+    from dmdqn_amd import ops
+    ops.load()
+    has = torch._C._dispatch_has_kernel_for_dispatch_key
+    for name in sorted(set(ops.ENTRY_POINTS.values())):
+        assert has(f"dmdqn::{name}", "CUDA"), name
+        assert has(f"dmdqn::{name}", "Meta"), name
+        assert not has(f"dmdqn::{name}", "CPU"), name
+
+
 def test_version_and_error_string(lib):
     # 4: dmdqn_source_digest, dmdqn_device_lds_per_cu (3: dmdqn_adam_slabs;
     # cap = physical ring slots; include/dmdqn.h)
